@@ -34,6 +34,8 @@ HBM_COPY_GBS = 6290.0   # measured float4 copy on the same chip (same guide)
 GATHER_CEILING_GBS = 7000.0   # whole-line fabric bytes of the bare memory pattern (tools/microbench/gather128.hip, gather_streams.hip: 6.9-7.0 TB/s)
 SEED = 0x5EED
 EXIT_GATHER_FAILED = 3  # the N>1 result-gather leg raised or ran into its deadline (the bench line is still printed)
+DUMP_NAMES = ("rgb", "pdf", "wo_sampled", "pdf_sampled", "weight")   # mrl_eval_sample_batch's outputs, in the order it returns them
+DUMP_UNITS = 1 << 20    # --dump-outputs keeps at most this many units: 44 MB of float32
 
 
 def host_cores() -> int:
@@ -108,6 +110,9 @@ def parse(argv=None):
                    help="MRL_OPT_TABLE_ARENA_MB: place the tables back to back in one device allocation of this size; -1 (default): 20 GB for "
                         "--config resident100 and 4 GB for mixed16_256m (address translation bounds those launches; one arena removes the slow mode "
                         "of the process-to-process spread and is worth 5 %%: profiles/r03_arena_ab.txt), none otherwise; 0: one allocation per table")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what rank 0's last step computed as DIR/<name>.npy (float32, one row per unit): "
+                        f"every unit when a step has at most {DUMP_UNITS}, else the same seeded sample of {DUMP_UNITS} units in ascending order")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-reps", type=int, default=5, help="repetitions of each CPU baseline leg (median is reported)")
     p.add_argument("--no-gather", action="store_true", help="N>1: skip the separately reported RCCL gather leg")
@@ -325,8 +330,25 @@ def cpu_baseline(ob, table, lookup: int, reps: int) -> dict:
     }
 
 
+def dump_outputs(directory: str, outs) -> None:
+    """Write the step's outputs (device tensors, one row per unit) as DIR/<name>.npy; a step of more than DUMP_UNITS units is
+    sampled at indices that depend only on its size, so that two builds run with the same arguments dump the same units."""
+    import numpy as np
+    import torch
+    n = int(outs[0].shape[0])
+    if n > DUMP_UNITS:
+        idx = np.sort(np.random.default_rng(SEED).choice(n, DUMP_UNITS, replace=False))
+        idx = torch.from_numpy(idx).to(outs[0].device)
+        outs = [o[idx] for o in outs]
+    os.makedirs(directory, exist_ok=True)
+    for name, o in zip(DUMP_NAMES, outs):
+        np.save(os.path.join(directory, name + ".npy"), o.cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     args = parse()
+    if args.dump_outputs and args.steps < 1:
+        sys.exit("bench.py: --dump-outputs writes what the last timed step computed and needs --steps >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))                         # before torch / the GPU are touched in this process
 
@@ -533,6 +555,9 @@ def main():
         },
         "roofline": roofline,
     }
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
 
     # ---- rank 0, N=1: parity sample vs the oracle + CPU baseline on the host cores ----
     if rank == 0:

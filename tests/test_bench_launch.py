@@ -117,3 +117,38 @@ def test_single_gpu_line_keeps_its_contract():
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["roofline"]["bytes_per_unit"] == 80 and out["config"]["materials_resident"] == 16
     assert out["parity"]["max_rel_err_vs_oracle"] <= 1e-6
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs: a step larger than bench.DUMP_UNITS is dumped as the same seeded sample on every run, and each dumped row is
+    what one direct mrl_eval_sample_batch call over the same generated inputs returns for that unit."""
+    import numpy as np
+    import torch
+    import bench
+    from mitsuba_customization_amd import host, synth
+
+    n = 3 * bench.DUMP_UNITS
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--units", str(n), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, env=_clean_env())
+        assert r.returncode == 0, r.stdout + r.stderr
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        dumps.append({k: np.load(d / f"{k}.npy") for k in bench.DUMP_NAMES})
+    for k in bench.DUMP_NAMES:
+        a, b = dumps[0][k], dumps[1][k]
+        assert a.dtype == np.float32 and a.shape[0] == bench.DUMP_UNITS and a.shape[1:] == ((3,) if k in ("rgb", "wo_sampled", "weight") else ())
+        assert np.array_equal(a, b), k
+    idx = np.sort(np.random.default_rng(bench.SEED).choice(n, bench.DUMP_UNITS, replace=False))
+    with host.MerlHip(0) as gpu:
+        gpu.use_torch_stream()                                        # as bench.py does: the indexing below is ordered after the kernel
+        mid = gpu.upload_merl(synth.make_table("ggx_tab", 0))
+        wi, wo, u = gpu.generate_pairs(bench.SEED, 0, n)
+        t = torch.from_numpy(idx).to(wi.device)
+        want = [x[t].cpu().numpy() for x in gpu.eval_sample(wi, wo, u, material=mid)]
+    for k, w in zip(bench.DUMP_NAMES, want):
+        got = dumps[0][k].astype(np.float64); w = w.astype(np.float64)
+        assert (np.abs(got - w) <= 1e-6 * np.abs(w) + 1e-30).all(), k

@@ -20,8 +20,7 @@ timeout -k 10 600 python3 tools/fuzz_parity_rgl.py 240 > "$OUT/fuzz_parity_rgl.j
 echo "rgl soak ok"
 timeout -k 10 600 python3 tools/fuzz_parity.py 96 > "$OUT/fuzz_parity.json" 2> "$OUT/fuzz_parity.err" || { echo "table soak failed"; tail -3 "$OUT/fuzz_parity.err"; exit 1; }
 echo "table soak ok"
-if [ -x tools/microbench/gather_quad ]; then
-  for mb in 1 13 36; do for m in scatter lane64 quadraw quad lane32 pair32; do timeout -k 10 60 tools/microbench/gather_quad $mb $m 4 || exit 1; done; done > "$OUT/gather_quad.jsonl" 2>&1
-  echo "microbench ok"
-fi
+hipcc -O3 --offload-arch=gfx950 -o tools/microbench/gather_quad tools/microbench/gather_quad.hip || { echo "gather_quad build failed"; exit 1; }
+for mb in 1 13 36; do for m in scatter lane64 quadraw quad lane32 pair32; do timeout -k 10 60 tools/microbench/gather_quad $mb $m 4 || exit 1; done; done > "$OUT/gather_quad.jsonl" 2>&1
+echo "microbench ok"
 echo done
