@@ -15,7 +15,7 @@ int ensure_stage(mrl_ctx *ctx, size_t units, size_t unit_bytes)
 }
 
 struct BatchCall {
-    int mode;                                    // 0 eval, 1 pdf, 2 sample, 3 eval+sample, 4 eval+pdf
+    int mode;                                    // a mrl::Mode
     const float *wi, *wo, *u;
     const int32_t *mat;
     int32_t single_id;
@@ -23,10 +23,6 @@ struct BatchCall {
     float *out_rgb, *out_pdf, *out_wo, *out_pdf2, *out_weight;
     int n_ch = 0;                                // 0: the RGB entry points; > 0: *_nch calls, out_rgb / out_weight are n x n_ch
 };
-
-inline bool call_has_eval(int mode) { return mode == 0 || mode == 3 || mode == 4; }
-inline bool call_has_pdf(int mode) { return mode == 1 || mode == 3 || mode == 4; }
-inline bool call_has_sample(int mode) { return mode == 2 || mode == 3; }
 
 
 int ensure_queues(mrl_ctx *ctx, size_t units)
@@ -70,7 +66,7 @@ DeviceCall device_call(const mrl_ctx *ctx, const BatchCall &c)
         if (d.multi && m.dev.kind != mrl::KIND_GGX && m.dev.param != mrl::PARAM_HALF_DIFF) a.any_standard = 1;
         d.has_ggx = d.has_ggx || m.dev.kind == mrl::KIND_GGX;
         d.has_table = d.has_table || m.dev.kind == mrl::KIND_MERL || m.dev.kind == mrl::KIND_TABLE ||
-                      (c.mode == 1 && m.dev.kind == mrl::KIND_TABLE_NCH);       // pdf serves n-channel tables too
+                      (c.mode == mrl::MODE_PDF && m.dev.kind == mrl::KIND_TABLE_NCH);       // pdf serves n-channel tables too
     }
     if (!d.has_ggx && !d.has_table) d.has_table = true;        // only tombstones left: the table path renders them as zeros
     if (!d.multi && a.single.kind != mrl::KIND_GGX && a.single.param != mrl::PARAM_HALF_DIFF) a.any_standard = 1;
@@ -80,7 +76,7 @@ DeviceCall device_call(const mrl_ctx *ctx, const BatchCall &c)
 // null-pointer and material checks shared by the whole-array and the queue entry points
 int check_call(mrl_ctx *ctx, const BatchCall &c)
 {
-    const bool has_eval = call_has_eval(c.mode), has_pdf = call_has_pdf(c.mode), has_sample = call_has_sample(c.mode);
+    const bool has_eval = mrl::mode_eval(c.mode), has_pdf = mrl::mode_pdf(c.mode), has_sample = mrl::mode_sample(c.mode);
     const bool needs_wo = has_eval || has_pdf, needs_u = has_sample;
     if (!c.wi || (needs_wo && !c.wo) || (needs_u && !c.u) || (has_eval && !c.out_rgb) || (has_pdf && !c.out_pdf) ||
         (has_sample && (!c.out_wo || !c.out_pdf2 || !c.out_weight)))
@@ -95,12 +91,12 @@ int check_call(mrl_ctx *ctx, const BatchCall &c)
             return MRL_OK;
         }
         if (d.kind == mrl::KIND_RGL_SPECTRAL) {                // the pdf is wavelength-free: the RGB pdf call serves it
-            if (c.mode == 1 && c.n_ch == 0) return MRL_OK;
+            if (c.mode == mrl::MODE_PDF && c.n_ch == 0) return MRL_OK;
             return fail(ctx, MRL_ERR_MATERIAL, "a spectral RGL material: use the mrl_*_spectral_batch entry points");
         }
-        if (c.n_ch == 0 && c.mode != 1 && !mrl::kind_is_rgb_path(d.kind))               // pdf is channel-free
+        if (c.n_ch == 0 && c.mode != mrl::MODE_PDF && !mrl::kind_is_rgb_path(d.kind))               // pdf is channel-free
             return fail(ctx, MRL_ERR_MATERIAL, "material has " + std::to_string(d.n_ch) + " channels: use the *_nch entry points");
-        if (c.n_ch > 0 && c.mode != 1 && (d.kind != mrl::KIND_TABLE_NCH || d.n_ch != c.n_ch))
+        if (c.n_ch > 0 && c.mode != mrl::MODE_PDF && (d.kind != mrl::KIND_TABLE_NCH || d.n_ch != c.n_ch))
             return fail(ctx, MRL_ERR_MATERIAL, "material does not have " + std::to_string(c.n_ch) + " channels");
     }
     return MRL_OK;
@@ -109,7 +105,7 @@ int check_call(mrl_ctx *ctx, const BatchCall &c)
 // host-or-device kind of the arrays a call of this mode touches (-1: mixed)
 int call_pointer_kind(const BatchCall &c, const void *extra0 = nullptr, const void *extra1 = nullptr)
 {
-    const bool has_eval = call_has_eval(c.mode), has_pdf = call_has_pdf(c.mode), has_sample = call_has_sample(c.mode);
+    const bool has_eval = mrl::mode_eval(c.mode), has_pdf = mrl::mode_pdf(c.mode), has_sample = mrl::mode_sample(c.mode);
     const bool needs_wo = has_eval || has_pdf, needs_u = has_sample;
     return common_kind({ c.wi, needs_wo ? c.wo : nullptr, needs_u ? c.u : nullptr, c.mat, extra0, extra1,
                          has_eval ? c.out_rgb : nullptr, has_pdf ? c.out_pdf : nullptr,
@@ -125,14 +121,14 @@ int launch_device(mrl_ctx *ctx, const BatchCall &c)
         MRL_HIP(ctx, mrl::launch_rgl(c.mode, a, &ctx->materials[(size_t)c.single_id].rgl, false, ctx->rgl_search, ctx->compute_units, ctx->stream));
         return MRL_OK;
     }
-    if (c.n_ch > 0 && c.mode != 1) {                          // n-channel tables: their own kernels (pdf is channel-free)
+    if (c.n_ch > 0 && c.mode != mrl::MODE_PDF) {                          // n-channel tables: their own kernels (pdf is channel-free)
         MRL_HIP(ctx, mrl::launch_batch_nch(c.mode, a, d.multi, c.n_ch, ctx->compute_units, ctx->stream));
         return MRL_OK;
     }
     const bool multi = d.multi, has_ggx = d.has_ggx, has_table = d.has_table;
     // MRL_OPT_KERNEL >= 4: a batch that may mix table and analytic materials is split into one dense queue
     // per kind (count / scan / partition, no atomics); each queue then runs through its dedicated kernel
-    if (multi && has_ggx && has_table && ctx->kernel_variant >= 4 && c.mode != 1 && ctx->table_layout == mrl::LAYOUT_BRICK &&
+    if (multi && has_ggx && has_table && ctx->kernel_variant >= 4 && c.mode != mrl::MODE_PDF && ctx->table_layout == mrl::LAYOUT_BRICK &&
         ctx->opts.lookup == 1 && c.n < ((size_t)1 << 32)) {
         uint32_t segments = 0, seg_len = 0;
         mrl::partition_geometry(c.n, ctx->compute_units, &segments, &seg_len);
@@ -161,7 +157,7 @@ int launch_device(mrl_ctx *ctx, const BatchCall &c)
 // -> copy-out (threads), double buffered so that the copies of chunks c+1 / c-1 overlap the kernel of chunk c.
 int run_host_pipelined(mrl_ctx *ctx, const BatchCall &c)
 {
-    const bool has_eval = call_has_eval(c.mode), has_pdf = call_has_pdf(c.mode), has_sample = call_has_sample(c.mode);
+    const bool has_eval = mrl::mode_eval(c.mode), has_pdf = mrl::mode_pdf(c.mode), has_sample = mrl::mode_sample(c.mode);
     const bool needs_wo = has_eval || has_pdf, needs_u = has_sample;
     const size_t C = c.n_ch > 0 ? (size_t)c.n_ch : 3;
     const size_t unit_bytes = 56 + 8 * C;
@@ -237,7 +233,7 @@ int run_batch(mrl_ctx *ctx, const BatchCall &c)
     if (!ctx) return MRL_ERR_INVALID;
     MRL_GUARD(ctx);
     if (c.n == 0) return MRL_OK;
-    const bool has_eval = call_has_eval(c.mode), has_pdf = call_has_pdf(c.mode), has_sample = call_has_sample(c.mode);
+    const bool has_eval = mrl::mode_eval(c.mode), has_pdf = mrl::mode_pdf(c.mode), has_sample = mrl::mode_sample(c.mode);
     const bool needs_wo = has_eval || has_pdf, needs_u = has_sample;
     int rc = check_call(ctx, c);
     if (rc != MRL_OK) return rc;
@@ -306,7 +302,7 @@ int run_queue(mrl_ctx *ctx, const BatchCall &c, const uint32_t *queue, const uin
         MRL_HIP(ctx, mrl::launch_rgl(c.mode, d.args, &ctx->materials[(size_t)c.single_id].rgl, true, ctx->rgl_search, ctx->compute_units, ctx->stream));
         return MRL_OK;
     }
-    if (c.n_ch > 0 && c.mode != 1) {                          // n-channel tables: the same kernels walk the queue
+    if (c.n_ch > 0 && c.mode != mrl::MODE_PDF) {                          // n-channel tables: the same kernels walk the queue
         MRL_HIP(ctx, mrl::launch_batch_nch(c.mode, d.args, d.multi, c.n_ch, ctx->compute_units, ctx->stream));
         return MRL_OK;
     }
@@ -322,34 +318,34 @@ extern "C" {
 
 int mrl_eval_batch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id, size_t n, float *out_rgb)
 {
-    BatchCall c{ 0, wi, wo, nullptr, mat, single_id, n, out_rgb, nullptr, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_EVAL, wi, wo, nullptr, mat, single_id, n, out_rgb, nullptr, nullptr, nullptr, nullptr };
     return run_batch(ctx, c);
 }
 
 int mrl_pdf_batch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id, size_t n, float *out_pdf)
 {
-    BatchCall c{ 1, wi, wo, nullptr, mat, single_id, n, nullptr, out_pdf, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_PDF, wi, wo, nullptr, mat, single_id, n, nullptr, out_pdf, nullptr, nullptr, nullptr };
     return run_batch(ctx, c);
 }
 
 int mrl_sample_batch(mrl_ctx *ctx, const float *wi, const float *u, const int32_t *mat, int32_t single_id, size_t n,
                      float *out_wo, float *out_pdf, float *out_weight)
 {
-    BatchCall c{ 2, wi, nullptr, u, mat, single_id, n, nullptr, nullptr, out_wo, out_pdf, out_weight };
+    BatchCall c{ mrl::MODE_SAMPLE, wi, nullptr, u, mat, single_id, n, nullptr, nullptr, out_wo, out_pdf, out_weight };
     return run_batch(ctx, c);
 }
 
 int mrl_eval_sample_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const int32_t *mat, int32_t single_id,
                           size_t n, float *out_rgb, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    BatchCall c{ 3, wi, wo, u, mat, single_id, n, out_rgb, out_pdf, out_wo, out_pdf2, out_weight };
+    BatchCall c{ mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, single_id, n, out_rgb, out_pdf, out_wo, out_pdf2, out_weight };
     return run_batch(ctx, c);
 }
 
 int mrl_eval_pdf_batch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id,
                        size_t n, float *out_rgb, float *out_pdf)
 {
-    BatchCall c{ 4, wi, wo, nullptr, mat, single_id, n, out_rgb, out_pdf, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_EVAL_PDF, wi, wo, nullptr, mat, single_id, n, out_rgb, out_pdf, nullptr, nullptr, nullptr };
     return run_batch(ctx, c);
 }
 
@@ -385,21 +381,21 @@ int mrl_partition_by_material(mrl_ctx *ctx, const int32_t *mat, size_t n, uint32
 int mrl_eval_pdf_queue(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id,
                        const uint32_t *queue, const uint32_t *queue_count, size_t capacity, float *out_rgb, float *out_pdf)
 {
-    BatchCall c = { 4, wi, wo, nullptr, mat, single_id, capacity, out_rgb, out_pdf, nullptr, nullptr, nullptr };
+    BatchCall c = { mrl::MODE_EVAL_PDF, wi, wo, nullptr, mat, single_id, capacity, out_rgb, out_pdf, nullptr, nullptr, nullptr };
     return run_queue(ctx, c, queue, queue_count);
 }
 
 int mrl_eval_queue(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id,
                    const uint32_t *queue, const uint32_t *queue_count, size_t capacity, float *out_rgb)
 {
-    BatchCall c = { 0, wi, wo, nullptr, mat, single_id, capacity, out_rgb, nullptr, nullptr, nullptr, nullptr };
+    BatchCall c = { mrl::MODE_EVAL, wi, wo, nullptr, mat, single_id, capacity, out_rgb, nullptr, nullptr, nullptr, nullptr };
     return run_queue(ctx, c, queue, queue_count);
 }
 
 int mrl_pdf_queue(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id,
                   const uint32_t *queue, const uint32_t *queue_count, size_t capacity, float *out_pdf)
 {
-    BatchCall c = { 1, wi, wo, nullptr, mat, single_id, capacity, nullptr, out_pdf, nullptr, nullptr, nullptr };
+    BatchCall c = { mrl::MODE_PDF, wi, wo, nullptr, mat, single_id, capacity, nullptr, out_pdf, nullptr, nullptr, nullptr };
     return run_queue(ctx, c, queue, queue_count);
 }
 
@@ -407,7 +403,7 @@ int mrl_sample_queue(mrl_ctx *ctx, const float *wi, const float *u, const int32_
                      const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
                      float *out_wo, float *out_pdf, float *out_weight)
 {
-    BatchCall c = { 2, wi, nullptr, u, mat, single_id, capacity, nullptr, nullptr, out_wo, out_pdf, out_weight };
+    BatchCall c = { mrl::MODE_SAMPLE, wi, nullptr, u, mat, single_id, capacity, nullptr, nullptr, out_wo, out_pdf, out_weight };
     return run_queue(ctx, c, queue, queue_count);
 }
 
@@ -416,7 +412,7 @@ int mrl_eval_sample_queue(mrl_ctx *ctx, const float *wi, const float *wo, const 
                           const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
                           float *out_rgb, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    BatchCall c = { 3, wi, wo, u, mat, single_id, capacity, out_rgb, out_pdf, out_wo, out_pdf2, out_weight };
+    BatchCall c = { mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, single_id, capacity, out_rgb, out_pdf, out_wo, out_pdf2, out_weight };
     return run_queue(ctx, c, queue, queue_count);
 }
 
@@ -461,21 +457,21 @@ static int nch_queue_call(mrl_ctx *ctx, BatchCall c, int n_channels, const uint3
 int mrl_eval_queue_nch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id, const uint32_t *queue,
                        const uint32_t *queue_count, size_t capacity, int n_channels, float *out_values)
 {
-    BatchCall c{ 0, wi, wo, nullptr, mat, single_id, capacity, out_values, nullptr, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_EVAL, wi, wo, nullptr, mat, single_id, capacity, out_values, nullptr, nullptr, nullptr, nullptr };
     return nch_queue_call(ctx, c, n_channels, queue, queue_count);
 }
 
 int mrl_sample_queue_nch(mrl_ctx *ctx, const float *wi, const float *u, const int32_t *mat, int32_t single_id, const uint32_t *queue,
                          const uint32_t *queue_count, size_t capacity, int n_channels, float *out_wo, float *out_pdf, float *out_weight)
 {
-    BatchCall c{ 2, wi, nullptr, u, mat, single_id, capacity, nullptr, nullptr, out_wo, out_pdf, out_weight };
+    BatchCall c{ mrl::MODE_SAMPLE, wi, nullptr, u, mat, single_id, capacity, nullptr, nullptr, out_wo, out_pdf, out_weight };
     return nch_queue_call(ctx, c, n_channels, queue, queue_count);
 }
 
 int mrl_eval_pdf_queue_nch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id, const uint32_t *queue,
                            const uint32_t *queue_count, size_t capacity, int n_channels, float *out_values, float *out_pdf)
 {
-    BatchCall c{ 4, wi, wo, nullptr, mat, single_id, capacity, out_values, out_pdf, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_EVAL_PDF, wi, wo, nullptr, mat, single_id, capacity, out_values, out_pdf, nullptr, nullptr, nullptr };
     return nch_queue_call(ctx, c, n_channels, queue, queue_count);
 }
 
@@ -483,35 +479,35 @@ int mrl_eval_sample_queue_nch(mrl_ctx *ctx, const float *wi, const float *wo, co
                               const uint32_t *queue, const uint32_t *queue_count, size_t capacity, int n_channels,
                               float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    BatchCall c{ 3, wi, wo, u, mat, single_id, capacity, out_values, out_pdf, out_wo, out_pdf2, out_weight };
+    BatchCall c{ mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, single_id, capacity, out_values, out_pdf, out_wo, out_pdf2, out_weight };
     return nch_queue_call(ctx, c, n_channels, queue, queue_count);
 }
 
 int mrl_eval_batch_nch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id, size_t n, int n_channels,
                        float *out_values)
 {
-    BatchCall c{ 0, wi, wo, nullptr, mat, single_id, n, out_values, nullptr, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_EVAL, wi, wo, nullptr, mat, single_id, n, out_values, nullptr, nullptr, nullptr, nullptr };
     return nch_call(ctx, c, n_channels);
 }
 
 int mrl_sample_batch_nch(mrl_ctx *ctx, const float *wi, const float *u, const int32_t *mat, int32_t single_id, size_t n, int n_channels,
                          float *out_wo, float *out_pdf, float *out_weight)
 {
-    BatchCall c{ 2, wi, nullptr, u, mat, single_id, n, nullptr, nullptr, out_wo, out_pdf, out_weight };
+    BatchCall c{ mrl::MODE_SAMPLE, wi, nullptr, u, mat, single_id, n, nullptr, nullptr, out_wo, out_pdf, out_weight };
     return nch_call(ctx, c, n_channels);
 }
 
 int mrl_eval_pdf_batch_nch(mrl_ctx *ctx, const float *wi, const float *wo, const int32_t *mat, int32_t single_id, size_t n, int n_channels,
                            float *out_values, float *out_pdf)
 {
-    BatchCall c{ 4, wi, wo, nullptr, mat, single_id, n, out_values, out_pdf, nullptr, nullptr, nullptr };
+    BatchCall c{ mrl::MODE_EVAL_PDF, wi, wo, nullptr, mat, single_id, n, out_values, out_pdf, nullptr, nullptr, nullptr };
     return nch_call(ctx, c, n_channels);
 }
 
 int mrl_eval_sample_batch_nch(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const int32_t *mat, int32_t single_id, size_t n,
                               int n_channels, float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    BatchCall c{ 3, wi, wo, u, mat, single_id, n, out_values, out_pdf, out_wo, out_pdf2, out_weight };
+    BatchCall c{ mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, single_id, n, out_values, out_pdf, out_wo, out_pdf2, out_weight };
     return nch_call(ctx, c, n_channels);
 }
 

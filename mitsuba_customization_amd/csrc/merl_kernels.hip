@@ -19,44 +19,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-enum Mode : int { MODE_EVAL = 0, MODE_PDF = 1, MODE_SAMPLE = 2, MODE_EVAL_SAMPLE = 3, MODE_EVAL_PDF = 4 };
-// what a mode computes: eval(wi, wo) -> rgb, pdf(wi, wo), sample(wi, u) -> (wo', pdf', weight')
-constexpr bool mode_eval(int m) { return m == MODE_EVAL || m == MODE_EVAL_SAMPLE || m == MODE_EVAL_PDF; }
-constexpr bool mode_pdf(int m) { return m == MODE_PDF || m == MODE_EVAL_SAMPLE || m == MODE_EVAL_PDF; }
-constexpr bool mode_sample(int m) { return m == MODE_SAMPLE || m == MODE_EVAL_SAMPLE; }
-
-__device__ __forceinline__ void load3(const float *p, size_t i, float &x, float &y, float &z)
-{
-    const float *q = p + 3 * i;
-    x = q[0]; y = q[1]; z = q[2];
-}
-__device__ __forceinline__ void store3(float *p, size_t i, const float v[3])
-{
-    float *q = p + 3 * i;
-    q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
-}
-// streaming (read-once / write-once) accesses: the nt hint keeps them from displacing table
-// lines in the XCD's L2
-template <bool NT> __device__ __forceinline__ float ldf(const float *p) { if constexpr (NT) return __builtin_nontemporal_load(p); else return *p; }
-template <bool NT> __device__ __forceinline__ void stf(float *p, float v) { if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v; }
-template <bool NT> __device__ __forceinline__ void load3s(const float *p, size_t i, float &x, float &y, float &z)
-{
-    const float *q = p + 3 * i;
-    x = ldf<NT>(q); y = ldf<NT>(q + 1); z = ldf<NT>(q + 2);
-}
-template <bool NT> __device__ __forceinline__ void store3s(float *p, size_t i, const float v[3])
-{
-    float *q = p + 3 * i;
-    stf<NT>(q, v[0]); stf<NT>(q + 1, v[1]); stf<NT>(q + 2, v[2]);
-}
-
-// number of work items of a launch: a.n, or for a queue launch the device-side count clamped to the capacity a.n
-template <bool INDEXED> __device__ __forceinline__ size_t item_count(const BatchArgs &a)
-{
-    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }
-    else return a.n;
-}
-
 // INDEXED: walk the queue a.idx[0 .. *a.idx_count) of unit indices instead of [0, n)
 template <int MODE, bool MULTI, bool INDEXED = false>
 __global__ __launch_bounds__(kBlock) void k_batch(BatchArgs a)
@@ -174,7 +136,7 @@ constexpr int kDmaBlock = MRL_DMA_BLOCK;
 // blocks of the LDS-DMA kernel one CU holds: 8 KB of LDS per wave and lookup (+ the exchange pages) out of 160 KB
 constexpr int dma_blocks_per_cu(int mode)
 {
-    const int lookups = (mode == 3 /* eval + sample */) ? 2 : 1;
+    const int lookups = mode == MODE_EVAL_SAMPLE ? 2 : 1;
     const int per_block = (kDmaBlock / 64) * lookups * (8192 + 512);
     return (160 * 1024) / per_block;
 }
@@ -920,13 +882,13 @@ __global__ __launch_bounds__(kBlock) void k_generate_materials(uint64_t seed, ui
     }
 }
 
-inline unsigned grid_for(size_t n, int compute_units)
+// 8 x 256-thread blocks per CU, grid-stride the rest
+inline unsigned grid_for(size_t n, int compute_units) { return grid_blocks(n, kBlock, (size_t)compute_units * 8); }
+// the LDS-DMA kernel: as many blocks as its LDS lets one CU hold (2 for the fused mode, 4 otherwise)
+template <int MODE>
+unsigned dma_grid(size_t n, int compute_units, bool whole_xcds)
 {
-    size_t blocks = (n + kBlock - 1) / kBlock;
-    size_t cap = (size_t)compute_units * 8;         // 8 x 256-thread blocks per CU, grid-stride the rest
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
+    return grid_blocks(n, kDmaBlock, (size_t)compute_units * dma_blocks_per_cu(MODE), whole_xcds);
 }
 
 // runtime (multi, nt, lookup, layout) -> compile-time kernel
@@ -975,12 +937,8 @@ hipError_t launch_mode(const BatchArgs &a, bool multi, int variant, int layout, 
     if constexpr (MODE != MODE_PDF) {
         // variant 3: cooperative LDS-DMA brick fetch (brick layout + trilinear only; otherwise variant 2)
         if (tuned && variant >= 3 && layout == LAYOUT_BRICK && a.opts.lookup == 1) {
-            // 64 KB (two lookups) or 32 KB (one) of LDS per 256-thread block: 2 or 4 blocks per CU
-            constexpr int per_cu = dma_blocks_per_cu(MODE);
-            size_t blocks = (a.n + kDmaBlock - 1) / kDmaBlock;
-            if (blocks > (size_t)compute_units * per_cu) blocks = (size_t)compute_units * per_cu;
-            blocks = (blocks + 7) / 8 * 8;                    // whole rounds over the 8 XCDs (BatchArgs::block_map)
-            const dim3 g((unsigned)blocks), b(kDmaBlock);
+            // 64 KB (two lookups) or 32 KB (one) of LDS per 256-thread block: 2 or 4 blocks per CU, whole rounds over the XCDs
+            const dim3 g(dma_grid<MODE>(a.n, compute_units, true)), b(kDmaBlock);
             if (multi && has_ggx)      MRL_DMA_LAUNCH(true, true, false);
             else if (multi)            MRL_DMA_LAUNCH(true, false, false);
             else                       MRL_DMA_LAUNCH(false, false, false);
@@ -1002,22 +960,14 @@ hipError_t launch_mode(const BatchArgs &a, bool multi, int variant, int layout, 
 hipError_t launch_batch(int mode, const BatchArgs &a, bool multi, int variant, int layout, bool has_ggx, bool has_table, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    switch (mode) {
-        case MODE_EVAL:        return launch_mode<MODE_EVAL>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_PDF:         return launch_mode<MODE_PDF>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_SAMPLE:      return launch_mode<MODE_SAMPLE>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_EVAL_SAMPLE: return launch_mode<MODE_EVAL_SAMPLE>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_EVAL_PDF:    return launch_mode<MODE_EVAL_PDF>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_mode(mode, [&](auto m) {
+        return launch_mode<decltype(m)::value>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
+    });
 }
 
 void partition_geometry(size_t n, int compute_units, uint32_t *segments, uint32_t *seg_len)
 {
-    size_t s = (n + kBlock - 1) / kBlock;
-    const size_t cap = (size_t)compute_units * 8;
-    if (s > cap) s = cap;
-    if (s < 1) s = 1;
+    const size_t s = grid_for(n, compute_units);
     size_t len = (n + s - 1) / s;
     len = (len + kBlock - 1) / kBlock * kBlock;
     *segments = (uint32_t)((n + len - 1) / len);
@@ -1048,10 +998,8 @@ hipError_t launch_queue_mode(const BatchArgs &a, bool ggx_queue, int compute_uni
         if (ggx_queue) {
             hipLaunchKernelGGL((k_ggx<MODE, true, true, true>), dim3(grid_for(a.n, compute_units)), dim3(kBlock), 0, stream, a);
         } else {
-            constexpr int per_cu = dma_blocks_per_cu(MODE);
-            size_t blocks = (a.n + kDmaBlock - 1) / kDmaBlock;
-            if (blocks > (size_t)compute_units * per_cu) blocks = (size_t)compute_units * per_cu;
-            const dim3 g((unsigned)blocks), b(kDmaBlock);
+            // not rounded to whole XCD rounds, unlike the other two DMA grids: block_map applies here only when the capped grid is a multiple of 8
+            const dim3 g(dma_grid<MODE>(a.n, compute_units, false)), b(kDmaBlock);
             MRL_DMA_LAUNCH(true, false, true);
         }
         return hipGetLastError();
@@ -1063,13 +1011,7 @@ hipError_t launch_queue_mode(const BatchArgs &a, bool ggx_queue, int compute_uni
 hipError_t launch_batch_queue(int mode, const BatchArgs &a, bool ggx_queue, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    switch (mode) {
-        case MODE_EVAL:        return launch_queue_mode<MODE_EVAL>(a, ggx_queue, compute_units, stream);
-        case MODE_SAMPLE:      return launch_queue_mode<MODE_SAMPLE>(a, ggx_queue, compute_units, stream);
-        case MODE_EVAL_SAMPLE: return launch_queue_mode<MODE_EVAL_SAMPLE>(a, ggx_queue, compute_units, stream);
-        case MODE_EVAL_PDF:    return launch_queue_mode<MODE_EVAL_PDF>(a, ggx_queue, compute_units, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_mode(mode, [&](auto m) { return launch_queue_mode<decltype(m)::value>(a, ggx_queue, compute_units, stream); });
 }
 
 namespace {
@@ -1087,11 +1029,7 @@ hipError_t launch_indexed_mode(const BatchArgs &a, bool multi, int layout, bool 
     }
     if constexpr (MODE != MODE_PDF) {
         if (layout == LAYOUT_BRICK && a.opts.lookup == 1) {
-            constexpr int per_cu = dma_blocks_per_cu(MODE);
-            size_t blocks = (a.n + kDmaBlock - 1) / kDmaBlock;
-            if (blocks > (size_t)compute_units * per_cu) blocks = (size_t)compute_units * per_cu;
-            blocks = (blocks + 7) / 8 * 8;
-            const dim3 g((unsigned)blocks), b(kDmaBlock);
+            const dim3 g(dma_grid<MODE>(a.n, compute_units, true)), b(kDmaBlock);
             if (multi && has_ggx)      MRL_DMA_LAUNCH(true, true, true);
             else if (multi)            MRL_DMA_LAUNCH(true, false, true);
             else                       MRL_DMA_LAUNCH(false, false, true);
@@ -1111,22 +1049,14 @@ hipError_t launch_batch_indexed(int mode, const BatchArgs &a, bool multi, int la
                                 int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    switch (mode) {
-        case MODE_EVAL:        return launch_indexed_mode<MODE_EVAL>(a, multi, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_PDF:         return launch_indexed_mode<MODE_PDF>(a, multi, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_SAMPLE:      return launch_indexed_mode<MODE_SAMPLE>(a, multi, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_EVAL_SAMPLE: return launch_indexed_mode<MODE_EVAL_SAMPLE>(a, multi, layout, has_ggx, has_table, compute_units, stream);
-        case MODE_EVAL_PDF:    return launch_indexed_mode<MODE_EVAL_PDF>(a, multi, layout, has_ggx, has_table, compute_units, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_mode(mode, [&](auto m) {
+        return launch_indexed_mode<decltype(m)::value>(a, multi, layout, has_ggx, has_table, compute_units, stream);
+    });
 }
 
 void material_partition_geometry(size_t n, int compute_units, uint32_t *chunks, uint32_t *chunk_len)
 {
-    size_t waves = (n + 63) / 64;
-    const size_t cap = (size_t)compute_units * 8 * kPartWaves;
-    if (waves > cap) waves = cap;
-    if (waves < 1) waves = 1;
+    size_t waves = grid_blocks(n, 64, (size_t)compute_units * 8 * kPartWaves);
     waves = (waves + kPartWaves - 1) / kPartWaves * kPartWaves;       // whole blocks
     size_t len = (n + waves - 1) / waves;
     len = (len + 63) / 64 * 64;

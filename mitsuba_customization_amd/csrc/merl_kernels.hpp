@@ -3,12 +3,45 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 #include <vector>
 
 #include "merl_device.hpp"
 #include "merl_image_file.hpp"       // RglFields / RglLayout, rgl_plan_layout, nch_brick_float4s: shapes -> sizes, pure host
 
 namespace mrl {
+
+// What a unit computes: eval(wi, wo) -> rgb, pdf(wi, wo), sample(wi, u) -> (wo', pdf', weight'), or one of two fusions.  Kernels
+// take the mode as an `int MODE` template parameter (their mangled names carry the number, and the ISA tests and profiles match on them).
+enum Mode : int { MODE_EVAL = 0, MODE_PDF = 1, MODE_SAMPLE = 2, MODE_EVAL_SAMPLE = 3, MODE_EVAL_PDF = 4 };
+constexpr bool mode_eval(int m) { return m == MODE_EVAL || m == MODE_EVAL_SAMPLE || m == MODE_EVAL_PDF; }
+constexpr bool mode_pdf(int m) { return m == MODE_PDF || m == MODE_EVAL_SAMPLE || m == MODE_EVAL_PDF; }
+constexpr bool mode_sample(int m) { return m == MODE_SAMPLE || m == MODE_EVAL_SAMPLE; }
+
+// runtime mode -> f(std::integral_constant<int, MODE>{}); hipErrorInvalidValue for a value that names no mode
+template <class F>
+hipError_t with_mode(int mode, F &&f)
+{
+    switch (mode) {
+        case MODE_EVAL:        return f(std::integral_constant<int, MODE_EVAL>{});
+        case MODE_PDF:         return f(std::integral_constant<int, MODE_PDF>{});
+        case MODE_SAMPLE:      return f(std::integral_constant<int, MODE_SAMPLE>{});
+        case MODE_EVAL_SAMPLE: return f(std::integral_constant<int, MODE_EVAL_SAMPLE>{});
+        case MODE_EVAL_PDF:    return f(std::integral_constant<int, MODE_EVAL_PDF>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// blocks of a grid-stride launch over n units at `threads` per block: at most cap, at least 1; whole_xcds: rounded up to whole
+// rounds over the 8 XCDs (workgroups are dealt to them round-robin; BatchArgs::block_map relies on it)
+inline unsigned grid_blocks(size_t n, size_t threads, size_t cap, bool whole_xcds = false)
+{
+    size_t blocks = (n + threads - 1) / threads;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    if (whole_xcds) blocks = (blocks + 7) / 8 * 8;
+    return (unsigned)blocks;
+}
 
 // Kernel arguments of one batched call; pointers are device-accessible.
 struct BatchArgs {
@@ -32,7 +65,40 @@ struct BatchArgs {
     const uint32_t *idx_count;               // its length, in device memory
 };
 
-// mode: 0 eval, 1 pdf, 2 sample, 3 eval+sample, 4 eval+pdf
+// ---- stream access of the batch kernels ----
+__device__ __forceinline__ void load3(const float *p, size_t i, float &x, float &y, float &z)
+{
+    const float *q = p + 3 * i;
+    x = q[0]; y = q[1]; z = q[2];
+}
+__device__ __forceinline__ void store3(float *p, size_t i, const float v[3])
+{
+    float *q = p + 3 * i;
+    q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
+}
+// streaming (read-once / write-once) accesses: the nt hint keeps them from displacing table
+// lines in the XCD's L2
+template <bool NT> __device__ __forceinline__ float ldf(const float *p) { if constexpr (NT) return __builtin_nontemporal_load(p); else return *p; }
+template <bool NT> __device__ __forceinline__ void stf(float *p, float v) { if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v; }
+template <bool NT> __device__ __forceinline__ void load3s(const float *p, size_t i, float &x, float &y, float &z)
+{
+    const float *q = p + 3 * i;
+    x = ldf<NT>(q); y = ldf<NT>(q + 1); z = ldf<NT>(q + 2);
+}
+template <bool NT> __device__ __forceinline__ void store3s(float *p, size_t i, const float v[3])
+{
+    float *q = p + 3 * i;
+    stf<NT>(q, v[0]); stf<NT>(q + 1, v[1]); stf<NT>(q + 2, v[2]);
+}
+
+// number of work items of a launch: a.n, or for a queue launch the device-side count clamped to the capacity a.n
+template <bool INDEXED> __device__ __forceinline__ size_t item_count(const BatchArgs &a)
+{
+    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }
+    else return a.n;
+}
+
+// mode: a Mode (MODE_EVAL .. MODE_EVAL_PDF)
 // variant: MRL_OPT_KERNEL (0 generic, 1 tuned table path, 2 + non-temporal streams, 3 + LDS-DMA brick fetch; 4 is handled by the caller)
 // layout: the context-wide table layout (every table of a context has the same one)
 // has_ggx / has_table: the context holds at least one analytic (GGX) / one table material, i.e. what a mixed batch may contain
@@ -66,7 +132,7 @@ hipError_t launch_build_sampling2d(const MaterialDev &m, const Options &opts, in
 // ---- n-channel tables (merl_nch.hip): a.out_rgb / a.out_weight hold n x n_ch values ----
 constexpr int kMaxChannels = 32;
 // nch_brick_float4s(n_ch): float4s per cell: 2 (1 ch), 4 (2 ch), 8 * ceil(n_ch / 4)  (merl_image_file.hpp)
-// mode: 0 eval, 2 sample, 3 eval+sample, 4 eval+pdf (pdf alone: the RGB pdf kernel serves every table kind)
+// mode: any but MODE_PDF (pdf alone: the RGB pdf kernel serves every table kind)
 hipError_t launch_batch_nch(int mode, const BatchArgs &a, bool multi, int n_ch, int compute_units, hipStream_t stream);
 hipError_t launch_build_table_nch(const double *d_planar, const double *d_scale, const int dims[3], int n_ch, int param, int clamp, float4 *d_out,
                                   int compute_units, hipStream_t stream);

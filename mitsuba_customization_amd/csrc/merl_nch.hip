@@ -24,22 +24,6 @@ namespace {
 
 constexpr int kNchBlock = 256;
 
-enum Mode : int { MODE_EVAL = 0, MODE_PDF = 1, MODE_SAMPLE = 2, MODE_EVAL_SAMPLE = 3, MODE_EVAL_PDF = 4 };
-constexpr bool mode_eval(int m) { return m == MODE_EVAL || m == MODE_EVAL_SAMPLE || m == MODE_EVAL_PDF; }
-constexpr bool mode_pdf(int m) { return m == MODE_PDF || m == MODE_EVAL_SAMPLE || m == MODE_EVAL_PDF; }
-constexpr bool mode_sample(int m) { return m == MODE_SAMPLE || m == MODE_EVAL_SAMPLE; }
-
-__device__ __forceinline__ void load3(const float *p, size_t i, float &x, float &y, float &z)
-{
-    const float *q = p + 3 * i;
-    x = q[0]; y = q[1]; z = q[2];
-}
-__device__ __forceinline__ void store3(float *p, size_t i, const float v[3])
-{
-    float *q = p + 3 * i;
-    q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
-}
-
 // piece swizzle of unit u for bricks of S pieces: any 16 lanes that one ds_read_b128 group serves
 // ({0-3, 12-15, 20-27} and its three siblings) then hit 16 different 16-B slots modulo 16
 template <int S> __device__ __forceinline__ unsigned nch_swz(unsigned u)
@@ -133,14 +117,9 @@ __device__ __forceinline__ void nch_blend(const float4 *lds_slots, unsigned lane
     }
 }
 
-// MODE as in merl_kernels.hip (pdf-only needs no table: the RGB pdf kernel serves every table kind).
+// MODE: any but MODE_PDF (pdf-only needs no table: the RGB pdf kernel serves every table kind).
 // a.out_rgb / a.out_weight hold n x n_ch values.
 // INDEXED: walk the caller's wavefront queue a.idx[0 .. min(*a.idx_count, a.n)) instead of the units [0, a.n)
-template <bool INDEXED> __device__ __forceinline__ size_t nch_item_count(const BatchArgs &a)
-{
-    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }
-    else return a.n;
-}
 
 template <int MODE, bool MULTI, int CPAD, bool INDEXED = false>
 __global__ __launch_bounds__(kNchBlock) void k_table_nch(BatchArgs a, int n_ch)
@@ -157,7 +136,7 @@ __global__ __launch_bounds__(kNchBlock) void k_table_nch(BatchArgs a, int n_ch)
     float4 *ldsB = lds[wave][LOOKUPS - 1];
     const int groups = CPAD == 4 ? (n_ch + 3) / 4 : 1;
     const size_t stride = (size_t)gridDim.x * kNchBlock;
-    const size_t n_items = nch_item_count<INDEXED>(a);
+    const size_t n_items = item_count<INDEXED>(a);
     const bool renorm = a.opts.negative == NEGATIVE_RENORMALISE;       // wave-uniform
     for (size_t base = (size_t)blockIdx.x * kNchBlock + wave * 64u; base < n_items; base += stride) {
         const size_t j = base + lane;
@@ -276,7 +255,7 @@ __global__ __launch_bounds__(kNchBlock) void k_table_nch_wide(BatchArgs a, int n
     float *stage = (float *)(dma + 64 * S);
     const int groups = (n_ch + 3) / 4;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const size_t n_items = nch_item_count<INDEXED>(a);
+    const size_t n_items = item_count<INDEXED>(a);
     const bool renorm = a.opts.negative == NEGATIVE_RENORMALISE;       // wave-uniform
     for (size_t base = (size_t)blockIdx.x * blockDim.x + wave * 64u; base < n_items; base += stride) {
         const size_t j = base + lane;
@@ -418,10 +397,7 @@ __global__ __launch_bounds__(kNchBlock) void k_build_bricks_nch(const double *pl
 template <int MODE, bool MULTI, bool INDEXED>
 hipError_t launch_nch_cpad(const BatchArgs &a, int n_ch, int compute_units, hipStream_t stream)
 {
-    size_t blocks = (a.n + kNchBlock - 1) / kNchBlock;
-    const size_t cap = (size_t)compute_units * (MODE == MODE_EVAL_SAMPLE ? 2 : 4);
-    if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(kNchBlock);
+    const dim3 g(grid_blocks(a.n, kNchBlock, (size_t)compute_units * (MODE == MODE_EVAL_SAMPLE ? 2 : 4))), b(kNchBlock);
     if (n_ch == 1)      hipLaunchKernelGGL((k_table_nch<MODE, MULTI, 1, INDEXED>), g, b, 0, stream, a, n_ch);
     else if (n_ch == 2) hipLaunchKernelGGL((k_table_nch<MODE, MULTI, 2, INDEXED>), g, b, 0, stream, a, n_ch);
     else if (n_ch == 4) hipLaunchKernelGGL((k_table_nch<MODE, MULTI, 4, INDEXED>), g, b, 0, stream, a, n_ch);   // one line, dense 16-B stores: both lookups in flight
@@ -431,10 +407,8 @@ hipError_t launch_nch_cpad(const BatchArgs &a, int n_ch, int compute_units, hipS
         // 4 waves per block while that fits 64 KB of LDS (up to 28 channels: 41 .. 62.5 KB), 2 waves beyond (32: 33.3 KB)
         const unsigned threads = (kNchBlock / 64) * wave_f4 * sizeof(float4) <= 65536 ? kNchBlock : kNchBlock / 2;
         const size_t lds = (threads / 64) * wave_f4 * sizeof(float4);
-        size_t wide_blocks = (a.n + threads - 1) / threads;
-        const size_t wide_cap = (size_t)compute_units * (threads == kNchBlock ? 2 : 4);       // 8 waves per CU either way
-        if (wide_blocks > wide_cap) wide_blocks = wide_cap;
-        hipLaunchKernelGGL((k_table_nch_wide<MODE, MULTI, INDEXED>), dim3((unsigned)wide_blocks), dim3(threads), lds, stream, a, n_ch);
+        const unsigned wide_blocks = grid_blocks(a.n, threads, (size_t)compute_units * (threads == kNchBlock ? 2 : 4));   // 8 waves per CU either way
+        hipLaunchKernelGGL((k_table_nch_wide<MODE, MULTI, INDEXED>), dim3(wide_blocks), dim3(threads), lds, stream, a, n_ch);
     }
     return hipGetLastError();
 }
@@ -442,8 +416,12 @@ hipError_t launch_nch_cpad(const BatchArgs &a, int n_ch, int compute_units, hipS
 template <int MODE>
 hipError_t launch_nch_mode(const BatchArgs &a, bool multi, bool indexed, int n_ch, int compute_units, hipStream_t stream)
 {
-    if (indexed) return multi ? launch_nch_cpad<MODE, true, true>(a, n_ch, compute_units, stream) : launch_nch_cpad<MODE, false, true>(a, n_ch, compute_units, stream);
-    return multi ? launch_nch_cpad<MODE, true, false>(a, n_ch, compute_units, stream) : launch_nch_cpad<MODE, false, false>(a, n_ch, compute_units, stream);
+    if constexpr (MODE == MODE_PDF) {
+        return hipErrorInvalidValue;                           // the RGB pdf kernel serves n-channel tables
+    } else {
+        if (indexed) return multi ? launch_nch_cpad<MODE, true, true>(a, n_ch, compute_units, stream) : launch_nch_cpad<MODE, false, true>(a, n_ch, compute_units, stream);
+        return multi ? launch_nch_cpad<MODE, true, false>(a, n_ch, compute_units, stream) : launch_nch_cpad<MODE, false, false>(a, n_ch, compute_units, stream);
+    }
 }
 
 } // namespace
@@ -453,13 +431,7 @@ hipError_t launch_batch_nch(int mode, const BatchArgs &a, bool multi, int n_ch, 
     if (a.n == 0) return hipSuccess;
     if (n_ch < 1 || n_ch > kMaxChannels || n_ch == 3) return hipErrorInvalidValue;
     const bool indexed = a.idx != nullptr;                     // a caller's wavefront queue (a.n = its capacity)
-    switch (mode) {
-        case MODE_EVAL:        return launch_nch_mode<MODE_EVAL>(a, multi, indexed, n_ch, compute_units, stream);
-        case MODE_SAMPLE:      return launch_nch_mode<MODE_SAMPLE>(a, multi, indexed, n_ch, compute_units, stream);
-        case MODE_EVAL_SAMPLE: return launch_nch_mode<MODE_EVAL_SAMPLE>(a, multi, indexed, n_ch, compute_units, stream);
-        case MODE_EVAL_PDF:    return launch_nch_mode<MODE_EVAL_PDF>(a, multi, indexed, n_ch, compute_units, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_mode(mode, [&](auto m) { return launch_nch_mode<decltype(m)::value>(a, multi, indexed, n_ch, compute_units, stream); });
 }
 
 hipError_t launch_build_table_nch(const double *d_planar, const double *d_scale, const int dims[3], int n_ch, int param, int clamp, float4 *d_out,
@@ -467,10 +439,7 @@ hipError_t launch_build_table_nch(const double *d_planar, const double *d_scale,
 {
     const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
     const size_t total = cells * (n_ch > 2 ? (size_t)((n_ch + 3) / 4) : 1);
-    size_t blocks = (total + kNchBlock - 1) / kNchBlock;
-    if (blocks > (size_t)compute_units * 8) blocks = (size_t)compute_units * 8;
-    if (blocks < 1) blocks = 1;
-    const dim3 g((unsigned)blocks), b(kNchBlock);
+    const dim3 g(grid_blocks(total, kNchBlock, (size_t)compute_units * 8)), b(kNchBlock);
     if (n_ch == 1)      hipLaunchKernelGGL((k_build_bricks_nch<1>), g, b, 0, stream, d_planar, d_scale, dims[0], dims[1], dims[2], (int)param_phi_periodic(param), n_ch, clamp, d_out);
     else if (n_ch == 2) hipLaunchKernelGGL((k_build_bricks_nch<2>), g, b, 0, stream, d_planar, d_scale, dims[0], dims[1], dims[2], (int)param_phi_periodic(param), n_ch, clamp, d_out);
     else                hipLaunchKernelGGL((k_build_bricks_nch<4>), g, b, 0, stream, d_planar, d_scale, dims[0], dims[1], dims[2], (int)param_phi_periodic(param), n_ch, clamp, d_out);

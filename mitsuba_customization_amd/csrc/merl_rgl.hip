@@ -36,9 +36,11 @@ constexpr int kRglBlock = 256;
 #endif
 constexpr int rgl_lds_block(int mode, int mask = 0)
 {
-    if (mode == 4 && mask == 5) return MRL_RGL_LDS_BLOCK_EVALPDF5;
-    return mode >= 2 ? (mask == 15 ? MRL_RGL_LDS_BLOCK_SAMPLE15 : MRL_RGL_LDS_BLOCK_SAMPLE) : MRL_RGL_LDS_BLOCK_EVAL;
+    if (mode == MODE_EVAL_PDF && mask == 5) return MRL_RGL_LDS_BLOCK_EVALPDF5;
+    return mode_sample(mode) || mode == MODE_EVAL_PDF ? (mask == 15 ? MRL_RGL_LDS_BLOCK_SAMPLE15 : MRL_RGL_LDS_BLOCK_SAMPLE) : MRL_RGL_LDS_BLOCK_EVAL;
 }
+// the grid-stride kernels (k_rgl, k_rgl_spectral without LDS): 8 blocks per CU
+inline unsigned rgl_grid(size_t n, int compute_units) { return grid_blocks(n, kRglBlock, (size_t)compute_units * 8); }
 
 // ---- the running integrals in LDS ----
 // Slice by slice (taken out of the records while they are copied: SearchLds below), for vndf and then luminance.  A ds_read gather of 64
@@ -217,8 +219,7 @@ __device__ __forceinline__ SearchLds stage_search(const WarpDev &w, unsigned &at
 template <int MODE, int MASK, class Grids, class Search>
 __device__ __forceinline__ void rgl_unit(const BatchArgs &a, const RglDev &r, const Grids &g, const Search &tv, const Search &tl, size_t i)
 {
-    constexpr bool has_eval = MODE == 0 || MODE == 3 || MODE == 4, has_pdf = MODE == 1 || MODE == 3 || MODE == 4,
-                   has_sample = MODE == 2 || MODE == 3;
+    constexpr bool has_eval = mode_eval(MODE), has_pdf = mode_pdf(MODE), has_sample = mode_sample(MODE);
     float wix = a.wi[3 * i], wiy = a.wi[3 * i + 1], wiz = a.wi[3 * i + 2];
     // (the unit's other stream reads are issued before the incident-only work waits for its own)
     float wox = 0.0f, woy = 0.0f, woz = 0.0f, u0 = 0.0f, u1 = 0.0f;
@@ -275,7 +276,8 @@ constexpr int rgl_min_blocks(int mode, bool multi, int mask)
     constexpr int b15[5] = { MRL_RGL_BLOCKS15 }, b5[5] = { MRL_RGL_BLOCKS5 };
     if (mask == 15) return b15[mode];
     if (mask == 5) return b5[mode];
-    return mode == 3 ? (multi ? MRL_RGL_MULTI_FUSED_BLOCKS : 2) : (mode == 2 ? MRL_RGL_SAMPLE_BLOCKS : (mode == 4 ? MRL_RGL_EVALPDF_BLOCKS : MRL_RGL_EVAL_BLOCKS));
+    return mode == MODE_EVAL_SAMPLE ? (multi ? MRL_RGL_MULTI_FUSED_BLOCKS : 2)
+         : mode == MODE_SAMPLE ? MRL_RGL_SAMPLE_BLOCKS : mode == MODE_EVAL_PDF ? MRL_RGL_EVALPDF_BLOCKS : MRL_RGL_EVAL_BLOCKS;
 }
 template <int MODE, bool INDEXED, bool MULTI, int MASK = 0>
 __global__ __launch_bounds__(kRglBlock, rgl_min_blocks(MODE, MULTI, MASK)) void k_rgl(BatchArgs a, RglDev r)
@@ -336,8 +338,7 @@ __global__ __launch_bounds__(rgl_lds_block(MODE, MASK)) void k_rgl_lds(BatchArgs
 template <int MODE, int MASK, class Search>
 __device__ __forceinline__ void rgl_unit_spectral(const BatchArgs &a, const RglDev &r, const GridLds &g, const Search &tv, const Search &tl, size_t i, const float *wl_all, int W)
 {
-    constexpr bool has_eval = MODE == 0 || MODE == 3 || MODE == 4, has_pdf = MODE == 1 || MODE == 3 || MODE == 4,
-                   has_sample = MODE == 2 || MODE == 3;
+    constexpr bool has_eval = mode_eval(MODE), has_pdf = mode_pdf(MODE), has_sample = mode_sample(MODE);
     const float wix = a.wi[3 * i], wiy = a.wi[3 * i + 1], wiz = a.wi[3 * i + 2];
     const float *wl = wl_all ? wl_all + i * (size_t)W : nullptr;
     rgl::Incident in;
@@ -399,7 +400,7 @@ hipError_t launch_masked(const BatchArgs &a, const RglDev *r, bool indexed, int 
     // LDS variant: a single-material launch large enough to pay for the copy (one image of the running integrals per CU)
     if (search == 0 && a.n >= (size_t)1 << 15) {
         // one workgroup per CU
-        auto grid_of = [&](int threads) { size_t blocks = (a.n + (size_t)threads - 1) / (size_t)threads; return dim3((unsigned)(blocks > (size_t)compute_units ? (size_t)compute_units : blocks)); };
+        auto grid_of = [&](int threads) { return dim3(grid_blocks(a.n, (size_t)threads, (size_t)compute_units)); };
         const size_t need = lds_bytes_of(*r), need_marg = lds_marg_bytes_of(*r);
         if (need <= (size_t)lds_limit()) {
             constexpr int kThreads = rgl_lds_block(MODE, kLdsMask);
@@ -414,7 +415,7 @@ hipError_t launch_masked(const BatchArgs &a, const RglDev *r, bool indexed, int 
         }
         // the marginal rows alone — sample() alone: eval / pdf read one marginal value per unit (not worth a copy per CU), and the fused
         // unit of such a file is issued as two launches (launch_rgl)
-        if constexpr (MODE == 2) {
+        if constexpr (MODE == MODE_SAMPLE) {
             if (need_marg <= (size_t)lds_limit()) {
                 constexpr int kThreads = rgl_lds_block(MODE, kMargMask);
                 if (indexed) {
@@ -428,11 +429,7 @@ hipError_t launch_masked(const BatchArgs &a, const RglDev *r, bool indexed, int 
             }
         }
     }
-    size_t blocks = (a.n + kRglBlock - 1) / kRglBlock;
-    const size_t cap = (size_t)compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(kRglBlock);
+    const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
     const size_t grids = grid_bytes_of(*r);                     // (at most 32 KB: 4,096 nodes per grid)
     if (indexed) hipLaunchKernelGGL((k_rgl<MODE, true, false, MASK>), grid, block, grids, stream, a, *r);
     else hipLaunchKernelGGL((k_rgl<MODE, false, false, MASK>), grid, block, grids, stream, a, *r);
@@ -443,11 +440,7 @@ template <int MODE>
 hipError_t launch_mode(const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream)
 {
     if (!r) {                                                   // a batch with material ids: descriptors come from the material array
-        size_t blocks = (a.n + kRglBlock - 1) / kRglBlock;
-        const size_t cap = (size_t)compute_units * 8;
-        if (blocks > cap) blocks = cap;
-        if (blocks < 1) blocks = 1;
-        const dim3 grid((unsigned)blocks), block(kRglBlock);
+        const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
         const RglDev none{};
         if (indexed) hipLaunchKernelGGL((k_rgl<MODE, true, true>), grid, block, 0, stream, a, none);
         else hipLaunchKernelGGL((k_rgl<MODE, false, true>), grid, block, 0, stream, a, none);
@@ -654,18 +647,12 @@ hipError_t launch_spectral_masked(const BatchArgs &a, const RglDev &r, const flo
         const size_t need = lds_bytes_of(r);
         if (need <= (size_t)lds_limit()) {
             constexpr int kThreads = rgl_lds_block(MODE);
-            size_t blocks = (a.n + kThreads - 1) / kThreads;
-            if (blocks > (size_t)compute_units) blocks = (size_t)compute_units;
             (void)hipFuncSetAttribute((const void *)k_rgl_spectral<MODE, true, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            hipLaunchKernelGGL((k_rgl_spectral<MODE, true, MASK>), dim3((unsigned)blocks), dim3(kThreads), need, stream, a, r, wl, W);
+            hipLaunchKernelGGL((k_rgl_spectral<MODE, true, MASK>), dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream, a, r, wl, W);
             return hipGetLastError();
         }
     }
-    size_t blocks = (a.n + kRglBlock - 1) / kRglBlock;
-    const size_t cap = (size_t)compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((k_rgl_spectral<MODE, false, MASK>), dim3((unsigned)blocks), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
+    hipLaunchKernelGGL((k_rgl_spectral<MODE, false, MASK>), dim3(rgl_grid(a.n, compute_units)), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
     return hipGetLastError();
 }
 // (the database's spectral files are isotropic: that shape has its own kernels, every other one tests the shape at run time)
@@ -681,14 +668,7 @@ hipError_t launch_spectral_mode(const BatchArgs &a, const RglDev &r, const float
 hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    switch (mode) {
-        case 0: return launch_spectral_mode<0>(a, r, wl, W, search, compute_units, stream);
-        case 1: return launch_spectral_mode<1>(a, r, wl, W, search, compute_units, stream);
-        case 2: return launch_spectral_mode<2>(a, r, wl, W, search, compute_units, stream);
-        case 3: return launch_spectral_mode<3>(a, r, wl, W, search, compute_units, stream);
-        case 4: return launch_spectral_mode<4>(a, r, wl, W, search, compute_units, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_mode(mode, [&](auto m) { return launch_spectral_mode<decltype(m)::value>(a, r, wl, W, search, compute_units, stream); });
 }
 
 hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream)
@@ -699,18 +679,11 @@ hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, bool indexe
     // 220 VGPRs through its eval as well (2 waves per SIMD); apart, eval + pdf runs at 3 waves per SIMD and sample() with its marginal
     // rows in LDS — 16M units: 3.84 ms fused, 3.34 ms apart (profiles/r04_rgl_rates.json); the 12 B per unit of wi read twice do not
     // show.  Same functions, same bits (the separate entry points are bit-compared with the fused one).
-    if (mode == 3 && r && search == 0 && a.n >= (size_t)1 << 15 && lds_bytes_of(*r) > (size_t)lds_limit()) {
-        const hipError_t e = launch_mode<4>(a, r, indexed, search, compute_units, stream);
-        return e != hipSuccess ? e : launch_mode<2>(a, r, indexed, search, compute_units, stream);
+    if (mode == MODE_EVAL_SAMPLE && r && search == 0 && a.n >= (size_t)1 << 15 && lds_bytes_of(*r) > (size_t)lds_limit()) {
+        const hipError_t e = launch_mode<MODE_EVAL_PDF>(a, r, indexed, search, compute_units, stream);
+        return e != hipSuccess ? e : launch_mode<MODE_SAMPLE>(a, r, indexed, search, compute_units, stream);
     }
-    switch (mode) {
-        case 0: return launch_mode<0>(a, r, indexed, search, compute_units, stream);
-        case 1: return launch_mode<1>(a, r, indexed, search, compute_units, stream);
-        case 2: return launch_mode<2>(a, r, indexed, search, compute_units, stream);
-        case 3: return launch_mode<3>(a, r, indexed, search, compute_units, stream);
-        case 4: return launch_mode<4>(a, r, indexed, search, compute_units, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_mode(mode, [&](auto m) { return launch_mode<decltype(m)::value>(a, r, indexed, search, compute_units, stream); });
 }
 
 } // namespace mrl

@@ -12,7 +12,7 @@ using namespace mrlabi;
 namespace {
 
 struct SpectralCall {
-    int mode;                                        // 0 eval, 2 sample, 3 eval + sample, 4 eval + pdf
+    int mode;                                        // a mrl::Mode other than MODE_PDF (the RGB pdf call serves these materials)
     const float *wi, *wo, *u, *wl;
     int W;
     int32_t id;
@@ -24,7 +24,7 @@ int run_spectral(mrl_ctx *ctx, const SpectralCall &c)
 {
     if (!ctx) return MRL_ERR_INVALID;
     MRL_GUARD(ctx);
-    const bool has_eval = c.mode == 0 || c.mode == 3 || c.mode == 4, has_pdf = c.mode == 3 || c.mode == 4, has_sample = c.mode == 2 || c.mode == 3;
+    const bool has_eval = mrl::mode_eval(c.mode), has_pdf = mrl::mode_pdf(c.mode), has_sample = mrl::mode_sample(c.mode);
     if (c.n == 0) return MRL_OK;
     if (!c.wi || (has_eval && (!c.wo || !c.out_values)) || (has_pdf && !c.out_pdf) || (has_sample && (!c.u || !c.out_wo || !c.out_pdf2 || !c.out_weight)))
         return fail(ctx, MRL_ERR_INVALID, "null array argument");
@@ -86,22 +86,22 @@ extern "C" {
 
 int mrl_eval_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, int32_t id, size_t n, float *out_values)
 {
-    return run_spectral(ctx, { 0, wi, wo, nullptr, wavelengths, n_wavelengths, id, n, out_values, nullptr, nullptr, nullptr, nullptr });
+    return run_spectral(ctx, { mrl::MODE_EVAL, wi, wo, nullptr, wavelengths, n_wavelengths, id, n, out_values, nullptr, nullptr, nullptr, nullptr });
 }
 int mrl_eval_pdf_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, int32_t id, size_t n,
                                 float *out_values, float *out_pdf)
 {
-    return run_spectral(ctx, { 4, wi, wo, nullptr, wavelengths, n_wavelengths, id, n, out_values, out_pdf, nullptr, nullptr, nullptr });
+    return run_spectral(ctx, { mrl::MODE_EVAL_PDF, wi, wo, nullptr, wavelengths, n_wavelengths, id, n, out_values, out_pdf, nullptr, nullptr, nullptr });
 }
 int mrl_sample_spectral_batch(mrl_ctx *ctx, const float *wi, const float *u, const float *wavelengths, int n_wavelengths, int32_t id, size_t n,
                               float *out_wo, float *out_pdf, float *out_weight)
 {
-    return run_spectral(ctx, { 2, wi, nullptr, u, wavelengths, n_wavelengths, id, n, nullptr, nullptr, out_wo, out_pdf, out_weight });
+    return run_spectral(ctx, { mrl::MODE_SAMPLE, wi, nullptr, u, wavelengths, n_wavelengths, id, n, nullptr, nullptr, out_wo, out_pdf, out_weight });
 }
 int mrl_eval_sample_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths, int32_t id,
                                    size_t n, float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    return run_spectral(ctx, { 3, wi, wo, u, wavelengths, n_wavelengths, id, n, out_values, out_pdf, out_wo, out_pdf2, out_weight });
+    return run_spectral(ctx, { mrl::MODE_EVAL_SAMPLE, wi, wo, u, wavelengths, n_wavelengths, id, n, out_values, out_pdf, out_wo, out_pdf2, out_weight });
 }
 
 int mrl_material_wavelengths(mrl_ctx *ctx, int id, int *n_wavelengths, float *out, size_t max_floats)
