@@ -259,17 +259,51 @@ def write_tensor_file(path: str, fields: dict) -> None:
 
 
 # ------------------------------------------------------------------ synthetic RGL *.bsdf fields (the adaptive parameterisation)
-def make_rgl_fields(seed: int = 0, n_phi: int = 1, n_theta: int = 6, res: int = 12, res_ndf: int = 16, res_sigma: int = 8, reduction: int = 1,
-                    n_wavelengths: int = 0) -> dict:
+def _xy(r):
+    """a table resolution: an int (square) or (nx, ny)"""
+    return (int(r), int(r)) if np.isscalar(r) else (int(r[0]), int(r[1]))
+
+
+def _zero_mass(a, how, n_phi, reduction):
+    """regions without mass in a distribution a [n_phi, n_theta, ny, nx], in place; keeps the periodic rows / slices equal"""
+    ny, nx = a.shape[-2:]
+    if how == "rows":
+        a[..., ny // 3:ny // 3 + 3, :] = 0.0
+        a[..., 0, :] = a[..., -1, :] = 0.0
+    elif how == "cols":
+        a[..., :, nx // 2:nx // 2 + 2] = 0.0
+        a[..., :, -2:] = 0.0
+    elif how == "slice":
+        ip = n_phi // 2 if n_phi > 2 else 0
+        a[ip, a.shape[1] // 2] = 0.0
+        if n_phi > 1 and reduction == 1 and ip in (0, n_phi - 1):
+            a[n_phi - 1 - ip, a.shape[1] // 2] = 0.0
+    elif how == "delta":
+        keep = a[..., ny // 2, nx - 1].copy()
+        a[...] = 0.0
+        a[..., ny // 2, nx - 1] = keep
+    else:
+        raise ValueError(how)
+
+
+def make_rgl_fields(seed: int = 0, n_phi: int = 1, n_theta: int = 6, res=12, res_ndf=16, res_sigma=8, reduction: int = 1,
+                    n_wavelengths: int = 0, grid: str = "even", sparse: str = "", sparse_in=("vndf", "luminance")) -> dict:
     """Fields of an RGL material-database file with the real names and shapes (what upstream Mitsuba 3's `measured` reads):
     phi_i [n_phi], theta_i [n_theta], ndf [res_ndf, res_ndf], sigma [res_sigma, res_sigma], vndf / luminance
     [n_phi, n_theta, res, res], rgb [n_phi, n_theta, 3, res, res], jacobian [1], description.  n_phi <= 2: isotropic.
     reduction = 2 / 4 (anisotropic only): phi_i covers [-pi, 0] / [-pi, -pi/2], as for a sample with a point symmetry / two mirror planes.
     n_wavelengths > 0: a SPECTRAL file — "spectra" [n_phi, n_theta, n_wavelengths, res, res] over "wavelengths" [n_wavelengths] (ascending,
     unevenly spaced on purpose, 360 - 1000 nm) instead of "rgb".
-    No measured file exists offline: the tables are smooth, strictly positive synthetic functions (a lobe + seeded
+    res / res_ndf / res_sigma: an int (square tables) or an (nx, ny) pair; arrays are [..., ny, nx], y the azimuth axis.
+    grid = "uneven": theta_i runs from 0.08 rad (a first elevation node above the normal) to 0.485 pi, denser toward grazing, and the
+    inner phi_i nodes are moved off the even spacing (the span and its ends stay: the file's reduction is unchanged).
+    sparse (applied to the distributions named in sparse_in): "rows" — node rows without mass (a band of three, and the periodic
+    rows 0 / ny - 1); "cols" — node columns without mass (a band inside, and the last two); "slice" — one whole (phi_i, theta_i) slice
+    without mass; "delta" — the mass of every slice in one node of the last column (two cells).
+    No measured file exists offline: by default the tables are smooth, strictly positive synthetic functions (a lobe + seeded
     low-frequency variation), periodic in every azimuth axis as a measurement is — they exercise every code path of the
-    model, they are not a material."""
+    model, they are not a material.  The defaults give the same arrays as before these options existed."""
+    res, res_ndf, res_sigma = (_xy(r) for r in (res, res_ndf, res_sigma))
     rng = np.random.default_rng(seed)
 
     def smooth(shape, lobe=2.0):
@@ -284,8 +318,17 @@ def make_rgl_fields(seed: int = 0, n_phi: int = 1, n_theta: int = 6, res: int = 
             flat[k] = 0.15 + np.exp(-lobe * a * (x - px) ** 2 - lobe * b * (y - py) ** 2) * (1.0 + 0.3 * np.sin(c * 6.0 * x) * np.cos(d * 5.0 * y))
         return out.astype(np.float32)
 
-    theta_i = np.linspace(0.0, 0.5 * np.pi * 0.97, n_theta).astype(np.float32)
-    phi_i = (np.zeros(1) if n_phi == 1 else np.linspace(-np.pi, -np.pi + 2 * np.pi / reduction, n_phi)).astype(np.float32)
+    if grid == "even":
+        theta_i = np.linspace(0.0, 0.5 * np.pi * 0.97, n_theta).astype(np.float32)
+        phi_i = (np.zeros(1) if n_phi == 1 else np.linspace(-np.pi, -np.pi + 2 * np.pi / reduction, n_phi)).astype(np.float32)
+    else:
+        assert grid == "uneven", grid
+        t = np.linspace(0.0, 1.0, n_theta)
+        theta_i = (0.08 + (0.5 * np.pi * 0.97 - 0.08) * (1.0 - (1.0 - t) ** 2) if n_theta > 1 else np.array([0.3])).astype(np.float32)
+        t = np.linspace(0.0, 1.0, n_phi)
+        phi_i = (np.zeros(1) if n_phi == 1 else -np.pi + 2 * np.pi / reduction * (t + 0.3 * np.sin(2 * np.pi * t) / (2 * np.pi))).astype(np.float32)
+        if n_phi > 1:
+            phi_i[0], phi_i[-1] = np.float32(-np.pi), np.float32(-np.pi + 2 * np.pi / reduction)
 
     def closed(a, slices_too=True):
         # the y axis of every warp is an azimuth (u = (phi + pi) / 2 pi): the rows at u = 0 and u = 1 are the same direction,
@@ -295,11 +338,15 @@ def make_rgl_fields(seed: int = 0, n_phi: int = 1, n_theta: int = 6, res: int = 
             a[-1] = a[0]
         return a
 
-    ndf = closed(smooth((res_ndf, res_ndf), 4.0), False)
-    sigma = closed((0.4 + smooth((res_sigma, res_sigma), 1.0)).astype(np.float32), False)
-    vndf, luminance = closed(smooth((n_phi, n_theta, res, res), 3.0)), closed(smooth((n_phi, n_theta, res, res), 1.0))
+    (nx, ny), (ndf_x, ndf_y), (sig_x, sig_y) = res, res_ndf, res_sigma
+    ndf = closed(smooth((ndf_y, ndf_x), 4.0), False)
+    sigma = closed((0.4 + smooth((sig_y, sig_x), 1.0)).astype(np.float32), False)
+    vndf, luminance = closed(smooth((n_phi, n_theta, ny, nx), 3.0)), closed(smooth((n_phi, n_theta, ny, nx), 1.0))
     n_values = n_wavelengths if n_wavelengths > 0 else 3
-    rgb = closed((0.05 + 0.5 * smooth((n_phi, n_theta, n_values, res, res), 1.5)).astype(np.float32))
+    rgb = closed((0.05 + 0.5 * smooth((n_phi, n_theta, n_values, ny, nx), 1.5)).astype(np.float32))
+    for name, a in (("vndf", vndf), ("luminance", luminance)):
+        if sparse and name in sparse_in:
+            _zero_mass(a, sparse, n_phi, reduction)
     if n_wavelengths > 0:
         steps = rng.uniform(0.5, 1.5, n_wavelengths)
         wl = 360.0 + np.concatenate([[0.0], np.cumsum(steps[:-1])]) * (640.0 / max(float(np.sum(steps[:-1])), 1e-9)) if n_wavelengths > 1 else np.array([550.0])

@@ -462,6 +462,14 @@ class OracleWarp:
             pass
 
 
+def half_vector_transverse(wi, wo):
+    """|m_xy| / |m| of the half vector m = wi / |wi| + wo / |wo| in f64, per pair (wi, wo: [3] or [n, 3]): the measure of how close a
+    pair is to the mirror configuration, where eval / pdf are ill-conditioned on both sides"""
+    a = np.asarray(wi, np.float64); b = np.asarray(wo, np.float64)
+    m = a / np.linalg.norm(a, axis=-1, keepdims=True) + b / np.linalg.norm(b, axis=-1, keepdims=True)
+    return np.hypot(m[..., 0], m[..., 1]) / np.linalg.norm(m, axis=-1)
+
+
 class OracleRgl:
     """The BSDF over the fields of an RGL *.bsdf file (dict of arrays: phi_i, theta_i, ndf, sigma, vndf, luminance, rgb[, jacobian])."""
 
@@ -571,7 +579,7 @@ class OracleRgl:
     def in_conditioning_range(self, what, got, wi, wo):
         """Is `got` — one unit's "eval" (3), "pdf" (1) or "weight" (3: eval / pdf) — where an evaluation of this ill-conditioned pair
         can land?  The sampled range of conditioning_range, widened on either side by a quarter of its width (the samples need not
-        hit the extremes) and by 2e-6 relative."""
+        hit the extremes) and by 1e-6 relative."""
         r = self.conditioning_range(wi, wo)
         if r is None:
             return False
@@ -583,8 +591,13 @@ class OracleRgl:
         else:
             lo, hi = lo[:3] / max(hi[3], 1e-300), hi[:3] / max(lo[3], 1e-300)
         g = np.asarray(got, np.float64).reshape(-1)
-        slack = 0.25 * (hi - lo) + 2e-6 * np.abs(hi) + 1e-30
+        slack = 0.25 * (hi - lo) + 1e-6 * np.abs(hi) + 1e-30
         return bool(np.all((g >= lo - slack) & (g <= hi + slack)))
+
+    def excused(self, what, got, wi, wo):
+        """May a unit whose value is beyond 1e-6 of the oracle's pass?  Only a near-mirror pair — transverse half vector at most 1e-6
+        (half_vector_transverse) — whose value lies in the oracle's own rounding range (in_conditioning_range)."""
+        return bool(half_vector_transverse(wi, wo) <= 1e-6) and self.in_conditioning_range(what, got, wi, wo)
 
     def __del__(self):
         try:

@@ -2,7 +2,8 @@
 // (csrc/merl_rgl.hip) compiled for the HOST, so that tests/test_rgl_cpu.py can compare them with oracle/rgl_oracle.c in a
 // container without a GPU.  No HIP runtime call is made.  Built by the test with hipcc.
 //   usage: rgl_host_harness <fields.bin> <pairs.bin> <out.bin>
-//   fields.bin: int32 n_phi n_theta res res_ndf res_sigma jacobian, then phi_i theta_i ndf sigma vndf luminance rgb (float32)
+//   fields.bin: int32 n_phi n_theta nx ny ndf_nx ndf_ny sigma_nx sigma_ny jacobian, then phi_i theta_i ndf sigma vndf luminance rgb (float32);
+//               every table [..][ny][nx]
 //   pairs.bin:  uint64 n, then wi[n][3] wo[n][3] u[n][2];   out.bin: n x 11 floats (rgb pdf | wo' pdf' weight')
 #include "../mitsuba_customization_amd/csrc/merl_rgl.hip"
 
@@ -10,22 +11,34 @@
 #include <cstdlib>
 #include <cstring>
 
-// --spectral <fields.bin> <pairs.bin> <out.bin>: fields.bin has a seventh int (n_wavelengths) and holds spectra + wavelengths in place
+// the fields of a file: the header's nine (spectral: ten) ints, then the arrays; `keep` owns them
+static bool read_fields(FILE *f, bool spectral, mrl::RglFields &F, std::vector<std::vector<float>> &keep)
+{
+    int h[10];
+    const size_t nh = spectral ? 10 : 9;
+    if (std::fread(h, 4, nh, f) != nh) return false;
+    F.n_phi = h[0]; F.n_theta = h[1]; F.res[0] = h[2]; F.res[1] = h[3]; F.res_ndf[0] = h[4]; F.res_ndf[1] = h[5]; F.res_sigma[0] = h[6]; F.res_sigma[1] = h[7];
+    F.jacobian = h[8];
+    F.n_wl = spectral ? h[9] : 0; F.wavelengths = nullptr;
+    if (mrl::rgl_check_shapes(F)) return false;
+    bool ok = true;
+    auto rd = [&](size_t n) { keep.emplace_back(n); ok = ok && std::fread(keep.back().data(), 4, n, f) == n; return keep.back().data(); };
+    const size_t per = (size_t)F.res[0] * F.res[1], sl = (size_t)F.n_phi * F.n_theta;
+    F.phi_i = rd(F.n_phi); F.theta_i = rd(F.n_theta); F.ndf = rd((size_t)F.res_ndf[0] * F.res_ndf[1]); F.sigma = rd((size_t)F.res_sigma[0] * F.res_sigma[1]);
+    F.vndf = rd(sl * per); F.luminance = rd(sl * per); F.rgb = rd(sl * per * (size_t)mrl::rgl_value_channels(F));
+    if (spectral) F.wavelengths = rd(F.n_wl);
+    return ok;
+}
+
+// --spectral <fields.bin> <pairs.bin> <out.bin>: fields.bin has a tenth int (n_wavelengths) and holds spectra + wavelengths in place
 // of rgb; pairs.bin: uint64 n, int32 W, wi wo u, then wavelengths [n][W]; out.bin: n x (values[W] pdf | wo'[3] pdf' weight'[W])
 static int spectral_main(char **argv)
 {
     FILE *f = std::fopen(argv[0], "rb");
     if (!f) return 3;
-    int h[7];
-    if (std::fread(h, 4, 7, f) != 7) return 3;
     mrl::RglFields F;
-    F.n_phi = h[0]; F.n_theta = h[1]; F.res[0] = F.res[1] = h[2]; F.res_ndf[0] = F.res_ndf[1] = h[3]; F.res_sigma[0] = F.res_sigma[1] = h[4]; F.jacobian = h[5];
-    F.n_wl = h[6];
     std::vector<std::vector<float>> keep;
-    auto rd = [&](size_t n) { keep.emplace_back(n); if (std::fread(keep.back().data(), 4, n, f) != n) std::exit(3); return keep.back().data(); };
-    const size_t per = (size_t)h[2] * h[2], sl = (size_t)h[0] * h[1];
-    F.phi_i = rd(h[0]); F.theta_i = rd(h[1]); F.ndf = rd((size_t)h[3] * h[3]); F.sigma = rd((size_t)h[4] * h[4]);
-    F.vndf = rd(sl * per); F.luminance = rd(sl * per); F.rgb = rd(sl * per * h[6]); F.wavelengths = rd(h[6]);
+    if (!read_fields(f, true, F, keep)) return 3;
     std::fclose(f);
     if (const char *why = mrl::rgl_check_fields(F)) { std::fprintf(stderr, "%s\n", why); return 4; }
     std::vector<float> blob;
@@ -58,16 +71,9 @@ int main(int argc, char **argv)
     if (argc < 4) return 2;
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) return 3;
-    int h[6];
-    if (std::fread(h, 4, 6, f) != 6) return 3;
     mrl::RglFields F;
-    F.n_phi = h[0]; F.n_theta = h[1]; F.res[0] = F.res[1] = h[2]; F.res_ndf[0] = F.res_ndf[1] = h[3]; F.res_sigma[0] = F.res_sigma[1] = h[4]; F.jacobian = h[5];
-    F.n_wl = 0; F.wavelengths = nullptr;
     std::vector<std::vector<float>> keep;
-    auto rd = [&](size_t n) { keep.emplace_back(n); if (std::fread(keep.back().data(), 4, n, f) != n) std::exit(3); return keep.back().data(); };
-    const size_t per = (size_t)h[2] * h[2], sl = (size_t)h[0] * h[1];
-    F.phi_i = rd(h[0]); F.theta_i = rd(h[1]); F.ndf = rd((size_t)h[3] * h[3]); F.sigma = rd((size_t)h[4] * h[4]);
-    F.vndf = rd(sl * per); F.luminance = rd(sl * per); F.rgb = rd(sl * per * 3);
+    if (!read_fields(f, false, F, keep)) return 3;
     std::fclose(f);
     if (const char *why = mrl::rgl_check_fields(F)) { std::fprintf(stderr, "%s\n", why); return 4; }
     std::vector<float> blob;
