@@ -21,6 +21,8 @@
  *   mrl_scalar_eval_sample                 ONE virtual BSDF::eval / sample / pdf call of a per-ray integrator
  *   mrl_*_queue                            the same calls over a wavefront integrator's material queue
  *                                          (the caller side of the path)
+ *   mrl_*_spectral_batch, _batch_mat,      spectral RGL materials (upstream `measured`, spectral variants): W values
+ *   mrl_*_spectral_queue                   per unit at the ray's own wavelengths; whole arrays, ids, wavefront queues
  *   mrl_material_release / mrl_memory_info plugin destructor (the host drops its last ref<BSDF>) / no counterpart
  *   mrl_material_*_nch, mrl_*_batch_nch,   customized_measurement tables with 1..32 channels (the
  *   mrl_*_queue_nch                        reference's own table format is unknown, Appendix B item 7)
@@ -155,7 +157,7 @@ enum mrl_option {
 enum mrl_material_kind { MRL_KIND_MERL = 0, MRL_KIND_TABLE = 1, MRL_KIND_GGX = 2, MRL_KIND_RELEASED = 3 /* tombstone, never reported */,
                          MRL_KIND_TABLE_NCH = 4 /* n-channel table: evaluated by the *_nch entry points only */,
                          MRL_KIND_RGL = 5 /* adaptive-parameterisation measured BSDF (mrl_material_upload_rgl) */,
-                         MRL_KIND_RGL_SPECTRAL = 6 /* the same from a spectral file: evaluated by the mrl_*_spectral_batch entry points */ };
+                         MRL_KIND_RGL_SPECTRAL = 6 /* the same from a spectral file: evaluated by the mrl_*_spectral_* entry points */ };
 
 /* ---- context ---- */
 int mrl_init(int device_id, mrl_ctx **out);
@@ -221,7 +223,8 @@ int mrl_material_load_rgl(mrl_ctx *ctx, const char *path, int *out_id);
  * passes PER UNIT — wavelengths [n][W], what hero-wavelength rendering carries per ray — or, with wavelengths == NULL, at the file's own
  * nodes (W must then be n_wavelengths: the n-channel form of the material, channel = node).  out_values / out_weight are [n][W];
  * pdf and the sampled direction do not depend on the wavelength; sample() reports eval / pdf AT the Float direction it returns, as for
- * RGB files.  Whole arrays, one material (no material-id array), host or device pointers (host arrays are staged in chunks).
+ * RGB files.  mrl_*_spectral_batch: whole arrays of one material, host or device pointers (host arrays are staged in chunks); the
+ * *_spectral_batch_mat and *_spectral_queue forms below take a material id per unit and / or a wavefront queue.
  * mrl_pdf_batch serves the kind too (the pdf is wavelength-free), mrl_material_load_rgl reads either variant,
  * mrl_material_save_image / _load_image and mrl_material_host_table take it; the RGB entry points answer MRL_ERR_MATERIAL for a
  * single_id of this kind and render it as zeros inside a batch with material ids.  PARITY UNPINNED (no spectral file exists offline;
@@ -243,6 +246,49 @@ int mrl_sample_spectral_batch(mrl_ctx *ctx, const float *wi, const float *u, con
                               float *out_wo, float *out_pdf, float *out_weight /* [n][W] */);
 int mrl_eval_sample_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths, int32_t id,
                                    size_t n, float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight);
+/* Spectral materials in a wavefront integrator (Mitsuba 3's scalar_spectral shape: every path carries its own hero wavelengths).
+ *   *_spectral_queue      the units queue[0 .. min(*queue_count, capacity)), with the conventions of the mrl_*_queue calls below:
+ *                         every input is read from and every output written to the queued slot (wavelengths[slot][..],
+ *                         out_values[slot][..], out_weight[slot][..], ...), other slots are left untouched; device pointers only
+ *                         (MRL_ERR_POINTER_MIX otherwise), capacity <= 2^32, asynchronous on the context's stream, capturable in a
+ *                         HIP graph; capacity == 0 does nothing.
+ *                         mat == NULL: the material single_id, which must be a live spectral RGL material (MRL_ERR_MATERIAL);
+ *                         wavelengths == NULL is then allowed with n_wavelengths == its node count, as in mrl_*_spectral_batch.
+ *   *_spectral_batch_mat  whole arrays [n] with a material id per unit; host or device pointers (host arrays, mat included, are staged
+ *                         in chunks of MRL_OPT_HOST_CHUNK units).
+ * With mat != NULL, wavelengths must not be NULL (MRL_ERR_INVALID): the materials of one call may have different node grids.  A unit
+ * whose id names no live spectral RGL material (out of range, released, an RGB RGL file, a table, GGX) gets zeros in every output of
+ * the call: W values, pdf, wo', pdf', W weights.  n_wavelengths (W) is 1..4096; a NULL output the mode writes is MRL_ERR_INVALID;
+ * the context's options act as in the whole-array call (MRL_OPT_RGL_SEARCH applies to a queue over one material; an RGL material
+ * follows its upstream plugin whatever MRL_OPT_COSINE_FACTOR says), and a queued or id-batched unit gets the bits the whole-array
+ * call of its material gives it.  The RGB entry points still answer MRL_ERR_MATERIAL for a spectral single_id and render a spectral
+ * id as zeros inside their batches with ids.
+ * Speed (eval + sample, 16M slots, W = 4, an isotropic 8 x 32 x 32 file with 32 nodes; profiles/r05_rgl_spectral_queue_rates.json):
+ * whole arrays 2.79 ms; a dense ascending queue over one material 2.77 ms, half the slots 1.72 ms, a shuffled dense queue 7.15 ms
+ * (the slot arrays are then read and written in scattered order).  With ids, two materials alternating: 5.51 ms, 1.54 x the 3.57 ms
+ * of mrl_partition_by_material plus one single_id queue call per material — the id kernel reads every lookup's parameter grids and
+ * search tables from memory through a per-unit descriptor, so a scene with few spectral materials is better served partitioned.
+ * PARITY UNPINNED, as for the whole-array calls. */
+int mrl_eval_spectral_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths /* [capacity][W] or NULL */, int n_wavelengths,
+                            const int32_t *mat, int32_t single_id, const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
+                            float *out_values /* [capacity][W] */);
+int mrl_eval_pdf_spectral_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths,
+                                const int32_t *mat, int32_t single_id, const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
+                                float *out_values, float *out_pdf);
+int mrl_sample_spectral_queue(mrl_ctx *ctx, const float *wi, const float *u, const float *wavelengths, int n_wavelengths,
+                              const int32_t *mat, int32_t single_id, const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
+                              float *out_wo, float *out_pdf, float *out_weight /* [capacity][W] */);
+int mrl_eval_sample_spectral_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths,
+                                   const int32_t *mat, int32_t single_id, const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
+                                   float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight);
+int mrl_eval_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths /* [n][W] */, int n_wavelengths,
+                                const int32_t *mat, size_t n, float *out_values);
+int mrl_eval_pdf_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths,
+                                    const int32_t *mat, size_t n, float *out_values, float *out_pdf);
+int mrl_sample_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *u, const float *wavelengths, int n_wavelengths,
+                                  const int32_t *mat, size_t n, float *out_wo, float *out_pdf, float *out_weight);
+int mrl_eval_sample_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths,
+                                       const int32_t *mat, size_t n, float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight);
 /* On-disk cache of a material's DEVICE image: what is resident for the material — the texels as Float (RGB tables
  * in the compact rows form, 24 MB for a MERL table, whatever the context's layout: a brick context expands them on the device), the
  * sampling marginal, the conditional sampling rows; for an RGL material the bracket-major image with its cell records — written so that
@@ -399,7 +445,8 @@ int mrl_material_load_tensor_table(mrl_ctx *ctx, const char *path, const char *f
  * the queue names; every other slot is left untouched.  queue_count lives in DEVICE memory (the
  * kernel that built the queue wrote it), so no host round trip separates queue building from the
  * BSDF call.  Device(-accessible) pointers only; asynchronous on the context's stream.  The caller
- * guarantees that every queued index addresses a valid slot of the arrays. ---- */
+ * guarantees that every queued index addresses a valid slot of the arrays.  Spectral RGL materials have
+ * queue calls of their own: mrl_*_spectral_queue above. ---- */
 /* Per-material compaction (wavefront ballot/prefix, no atomics): a stable partition of the slots [0, n) by
  * material id.  queue_out[n] receives the slot indices grouped by material, ascending inside each group;
  * offsets_out[mrl_material_count() + 1]: group m is queue_out[offsets[m] .. offsets[m + 1]);

@@ -150,6 +150,10 @@ hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, bool indexe
 // a spectral RGL material: a.out_rgb / a.out_weight hold n x W values at the per-unit wavelengths wl [n][W] (nullptr: the file's own
 // wavelength nodes, W = their number); single material, whole arrays
 hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream);
+// the same over a queue (indexed: a.idx / a.idx_count, a.n = the capacity) and / or with a material id per unit (r == nullptr: a.mat,
+// a.materials; a unit whose id names no live spectral RGL material gets zeros in every output of the mode); any mode but MODE_PDF
+hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, bool indexed, const float *wl, int W, int search, int compute_units,
+                                 hipStream_t stream);
 // ---- one-unit calls (merl_scalar.hip): a bounded-lifetime service kernel answers requests posted in pinned host memory ----
 struct ScalarBoard;
 struct ScalarArgs {

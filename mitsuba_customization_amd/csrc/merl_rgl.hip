@@ -7,6 +7,7 @@
 //                                              integrals come from the cell records in memory
 //   k_rgl_lds<MODE, INDEXED, MARG_ONLY, MASK>  one workgroup per CU first copies those integrals (or the marginal rows alone) into LDS
 //   k_rgl_spectral<MODE, LDS, MASK>            the same for spectral files, W values per unit
+//   k_rgl_spectral_q<MODE, INDEXED, MULTI, LDS, MASK>  spectral files over a wavefront queue (one material) or with a material id per unit
 // MASK: the bracket shape the kernel is compiled for (5 isotropic, 15 anisotropic, 0 tested at run time).  What bounds them — round
 // trips, then L1 line fills, then (isotropic) the vector ALU — and the measured rates: merl_rgl.hpp's header, DESIGN.md §5e.
 #include "merl_kernels.hpp"
@@ -335,8 +336,8 @@ __global__ __launch_bounds__(rgl_lds_block(MODE, MASK)) void k_rgl_lds(BatchArgs
 
 // ---- spectral files: W values per unit at the wavelengths wl[i * W .. ) (nullptr: the file's own nodes) ----
 // a.out_rgb / a.out_weight hold n x W values.  Same structure as rgl_unit: what depends on wi alone is formed once.
-template <int MODE, int MASK, class Search>
-__device__ __forceinline__ void rgl_unit_spectral(const BatchArgs &a, const RglDev &r, const GridLds &g, const Search &tv, const Search &tl, size_t i, const float *wl_all, int W)
+template <int MODE, int MASK, class Grids, class Search>
+__device__ __forceinline__ void rgl_unit_spectral(const BatchArgs &a, const RglDev &r, const Grids &g, const Search &tv, const Search &tl, size_t i, const float *wl_all, int W)
 {
     constexpr bool has_eval = mode_eval(MODE), has_pdf = mode_pdf(MODE), has_sample = mode_sample(MODE);
     const float wix = a.wi[3 * i], wiy = a.wi[3 * i + 1], wiz = a.wi[3 * i + 2];
@@ -378,6 +379,56 @@ __global__ __launch_bounds__(LDS ? rgl_lds_block(MODE) : kRglBlock) void k_rgl_s
         __syncthreads();
         for (size_t i = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; i < a.n; i += stride)
             rgl_unit_spectral<MODE, MASK>(a, r, grids, rgl::SearchMem(r.vndf()), rgl::SearchMem(r.luminance()), i, wl, W);
+    }
+}
+
+// ---- spectral files over a wavefront queue, or with a material id per unit ----
+// INDEXED: the units a.idx[0 .. min(*a.idx_count, a.n)); every read and write is at the queued slot (wl[i * W ..], out_rgb[i * W ..], ...)
+// and slots not in the queue are not touched.  !MULTI: the launch's one material, the body of k_rgl_spectral (grids in LDS, LDS: the
+// search tables as well).  MULTI: the material per unit from a.mat; a lane whose id names no live spectral RGL material writes zeros to
+// every output of its mode (W values, pdf, wo', pdf', W weights).
+template <int MODE>
+__device__ __forceinline__ void spectral_zeros(const BatchArgs &a, size_t i, int W)
+{
+    if constexpr (mode_eval(MODE)) for (int k = 0; k < W; ++k) a.out_rgb[i * (size_t)W + (size_t)k] = 0.0f;
+    if constexpr (mode_pdf(MODE)) a.out_pdf[i] = 0.0f;
+    if constexpr (mode_sample(MODE)) {
+        a.out_wo[3 * i] = 0.0f; a.out_wo[3 * i + 1] = 0.0f; a.out_wo[3 * i + 2] = 0.0f;
+        a.out_pdf2[i] = 0.0f;
+        for (int k = 0; k < W; ++k) a.out_weight[i * (size_t)W + (size_t)k] = 0.0f;
+    }
+}
+
+template <int MODE, bool INDEXED, bool MULTI, bool LDS, int MASK = 0>
+__global__ __launch_bounds__(LDS ? rgl_lds_block(MODE) : kRglBlock) void k_rgl_spectral_q(BatchArgs a, RglDev r, const float *wl, int W)
+{
+    static_assert(!(MULTI && LDS), "a batch with ids reads its materials' tables from memory");
+    constexpr int kBlockThreads = LDS ? rgl_lds_block(MODE) : kRglBlock;
+    const size_t stride = (size_t)gridDim.x * kBlockThreads;
+    const size_t n_items = item_count<INDEXED>(a);
+    if constexpr (MULTI) {
+        for (size_t j = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; j < n_items; j += stride) {
+            const size_t i = INDEXED ? (size_t)a.idx[j] : j;
+            const int id = a.mat[i];
+            if (id < 0 || id >= a.n_materials || a.materials[id].kind != KIND_RGL_SPECTRAL) { spectral_zeros<MODE>(a, i, W); continue; }
+            // the descriptor into registers, whole (as k_rgl MULTI)
+            const RglDev rm = *(const RglDev *)a.materials[id].rgl;
+            rgl_unit_spectral<MODE, 0>(a, rm, rgl::GridMem{ rm.phi, rm.theta, rm.wavelengths }, rgl::SearchMem(rm.vndf()), rgl::SearchMem(rm.luminance()), i, wl, W);
+        }
+    } else {
+        unsigned at = 0;
+        const GridLds grids = stage_grids(r, at, kBlockThreads);
+        if constexpr (LDS) {
+            const SearchLds tv = stage_search(r.vndf(), at, kBlockThreads);
+            const SearchLds tl = stage_search(r.luminance(), at, kBlockThreads);
+            __syncthreads();
+            for (size_t j = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; j < n_items; j += stride)
+                rgl_unit_spectral<MODE, MASK>(a, r, grids, tv, tl, INDEXED ? (size_t)a.idx[j] : j, wl, W);
+        } else {
+            __syncthreads();
+            for (size_t j = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; j < n_items; j += stride)
+                rgl_unit_spectral<MODE, MASK>(a, r, grids, rgl::SearchMem(r.vndf()), rgl::SearchMem(r.luminance()), INDEXED ? (size_t)a.idx[j] : j, wl, W);
+        }
     }
 }
 
@@ -663,7 +714,50 @@ hipError_t launch_spectral_mode(const BatchArgs &a, const RglDev &r, const float
     return launch_spectral_masked<MODE, 0>(a, r, wl, W, search, compute_units, stream);
 }
 
+// a queue over one material: the launch choice of launch_spectral_masked
+template <int MODE, int MASK>
+hipError_t launch_spectral_queue_masked(const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
+{
+    if (search == 0 && a.n >= (size_t)1 << 15) {
+        const size_t need = lds_bytes_of(r);
+        if (need <= (size_t)lds_limit()) {
+            constexpr int kThreads = rgl_lds_block(MODE);
+            (void)hipFuncSetAttribute((const void *)k_rgl_spectral_q<MODE, true, false, true, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
+            hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, false, true, MASK>), dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream,
+                               a, r, wl, W);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, false, false, MASK>), dim3(rgl_grid(a.n, compute_units)), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
+    return hipGetLastError();
+}
+template <int MODE>
+hipError_t launch_spectral_queue_mode(const BatchArgs &a, const RglDev *r, bool indexed, const float *wl, int W, int search, int compute_units, hipStream_t stream)
+{
+    if (!r) {                                                   // material ids: descriptors come from the material array
+        const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
+        const RglDev none{};
+        if (indexed) hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, true, false>), grid, block, 0, stream, a, none, wl, W);
+        else hipLaunchKernelGGL((k_rgl_spectral_q<MODE, false, true, false>), grid, block, 0, stream, a, none, wl, W);
+        return hipGetLastError();
+    }
+    if (!indexed) return launch_spectral_mode<MODE>(a, *r, wl, W, search, compute_units, stream);
+    if (r->n_phi == 1 && r->n_theta > 1) return launch_spectral_queue_masked<MODE, 5>(a, *r, wl, W, search, compute_units, stream);
+    return launch_spectral_queue_masked<MODE, 0>(a, *r, wl, W, search, compute_units, stream);
+}
+
 } // namespace
+
+hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, bool indexed, const float *wl, int W, int search, int compute_units,
+                                 hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    return with_mode(mode, [&](auto m) -> hipError_t {
+        constexpr int M = decltype(m)::value;
+        if constexpr (M == MODE_PDF) return hipErrorInvalidValue;       // (the pdf is wavelength-free: the RGB pdf calls serve these materials)
+        else return launch_spectral_queue_mode<M>(a, r, indexed, wl, W, search, compute_units, stream);
+    });
+}
 
 hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
 {

@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "mrl_material_upload_rgl_spectral", "mrl_material_wavelengths", "mrl_eval_spectral_batch", "mrl_eval_pdf_spectral_batch",
     "mrl_sample_spectral_batch", "mrl_eval_sample_spectral_batch", "mrl_host_eval_pdf_spectral", "mrl_host_sample_spectral",
     "mrl_group_material_upload_rgl_spectral",
+    "mrl_eval_spectral_queue", "mrl_eval_pdf_spectral_queue", "mrl_sample_spectral_queue", "mrl_eval_sample_spectral_queue",
+    "mrl_eval_spectral_batch_mat", "mrl_eval_pdf_spectral_batch_mat", "mrl_sample_spectral_batch_mat", "mrl_eval_sample_spectral_batch_mat",
 )
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
@@ -265,6 +267,14 @@ def load_library(path: Optional[str] = None):
     L.mrl_eval_pdf_spectral_batch.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_sample_spectral_batch.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp, fp, fp]
     L.mrl_eval_sample_spectral_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp, fp, fp, fp, fp]
+    L.mrl_eval_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp]
+    L.mrl_eval_pdf_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
+    L.mrl_sample_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp]
+    L.mrl_eval_sample_spectral_queue.argtypes = [vp, fp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp, fp, fp]
+    L.mrl_eval_spectral_batch_mat.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp]
+    L.mrl_eval_pdf_spectral_batch_mat.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp, fp]
+    L.mrl_sample_spectral_batch_mat.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp, fp, fp]
+    L.mrl_eval_sample_spectral_batch_mat.argtypes = [vp, fp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp, fp, fp, fp, fp]
     cfp = C.POINTER(C.c_float)
     L.mrl_host_eval_pdf_spectral.argtypes = [vp, cfp, cfp, cfp, C.c_int, cfp, cfp]
     L.mrl_host_sample_spectral.argtypes = [vp, cfp, cfp, cfp, C.c_int, cfp, cfp, cfp]
@@ -482,6 +492,51 @@ class MerlHip:
             _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf"), _addr(w, np.float32, W, n, "out_weight")), "mrl_sample_spectral_batch")
         return wo2, pdf2, w
 
+    # ---- spectral materials with a material id per unit (whole arrays: host or device) ----
+    # A unit whose id names no live spectral RGL material gets zeros; wavelengths [n, W] are required (materials may have different
+    # node grids).  PARITY UNPINNED, as for the single-material calls.
+    def eval_sample_spectral_mat(self, wi, wo, u, wavelengths, mat):
+        """(values [n, W], pdf, wo', pdf', weight' [n, W]) of the material mat[i] at wavelengths[i]."""
+        n = int(wi.shape[0]); self._prep(wi)
+        W = int(wavelengths.shape[1])
+        out = (self._empty(wi, (n, W)), self._empty(wi, (n,)), self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, W)))
+        val, pdf, wo2, pdf2, w = out
+        self._check(self._lib.mrl_eval_sample_spectral_batch_mat(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
+            _addr(wavelengths, np.float32, W, n, "wavelengths"), W, _addr(mat, np.int32, None, n, "mat"), n,
+            _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"), _addr(wo2, np.float32, 3, n, "out_wo"),
+            _addr(pdf2, np.float32, None, n, "out_pdf2"), _addr(w, np.float32, W, n, "out_weight")), "mrl_eval_sample_spectral_batch_mat")
+        return out
+
+    def eval_spectral_mat(self, wi, wo, wavelengths, mat):
+        n = int(wi.shape[0]); self._prep(wi)
+        W = int(wavelengths.shape[1])
+        val = self._empty(wi, (n, W))
+        self._check(self._lib.mrl_eval_spectral_batch_mat(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
+            _addr(mat, np.int32, None, n, "mat"), n, _addr(val, np.float32, W, n, "out_values")), "mrl_eval_spectral_batch_mat")
+        return val
+
+    def eval_pdf_spectral_mat(self, wi, wo, wavelengths, mat):
+        n = int(wi.shape[0]); self._prep(wi)
+        W = int(wavelengths.shape[1])
+        val, pdf = self._empty(wi, (n, W)), self._empty(wi, (n,))
+        self._check(self._lib.mrl_eval_pdf_spectral_batch_mat(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
+            _addr(mat, np.int32, None, n, "mat"), n, _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf")),
+            "mrl_eval_pdf_spectral_batch_mat")
+        return val, pdf
+
+    def sample_spectral_mat(self, wi, u, wavelengths, mat):
+        n = int(wi.shape[0]); self._prep(wi)
+        W = int(wavelengths.shape[1])
+        wo2, pdf2, w = self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, W))
+        self._check(self._lib.mrl_sample_spectral_batch_mat(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
+            _addr(mat, np.int32, None, n, "mat"), n, _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf"),
+            _addr(w, np.float32, W, n, "out_weight")), "mrl_sample_spectral_batch_mat")
+        return wo2, pdf2, w
+
     def load_rgl(self, path: str) -> int:
         """An RGL *.bsdf file (tensor_file container with the RGL field names; the *_rgb variant)."""
         mid = C.c_int()
@@ -676,6 +731,59 @@ class MerlHip:
                                                      _addr(val, np.float32, n_channels, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf")),
                     "mrl_eval_pdf_queue_nch")
         return val, pdf
+
+    # ---- spectral materials over a wavefront queue (GPU tensors only) ----
+    # wavelengths [n, W] per slot (None: the file's own nodes, n_wavelengths = their number; single material only); mat: a material id
+    # per slot (None: `material`).  Unqueued slots of `out` stay as they are.  PARITY UNPINNED, as for the whole-array calls.
+    def _spectral_w(self, wavelengths, n_wavelengths):
+        return int(wavelengths.shape[1]) if wavelengths is not None else int(n_wavelengths)
+
+    def eval_sample_spectral_queue(self, wi, wo, u, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
+                                   n_wavelengths: Optional[int] = None):
+        """Fused spectral unit over a wavefront queue: (values [n, W], pdf, wo', pdf', weight' [n, W])."""
+        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
+        W = self._spectral_w(wavelengths, n_wavelengths)
+        if out is None:
+            out = (self._zeros(wi, (n, W)), self._zeros(wi, (n,)), self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, W)))
+        val, pdf, wo2, pdf2, w = out
+        self._check(self._lib.mrl_eval_sample_spectral_queue(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
+            _addr(wavelengths, np.float32, W, n, "wavelengths"), W, _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
+            _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"), _addr(wo2, np.float32, 3, n, "out_wo"),
+            _addr(pdf2, np.float32, None, n, "out_pdf2"), _addr(w, np.float32, W, n, "out_weight")), "mrl_eval_sample_spectral_queue")
+        return out
+
+    def eval_spectral_queue(self, wi, wo, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
+                            n_wavelengths: Optional[int] = None):
+        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
+        W = self._spectral_w(wavelengths, n_wavelengths)
+        out = self._zeros(wi, (n, W)) if out is None else out
+        self._check(self._lib.mrl_eval_spectral_queue(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
+            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, _addr(out, np.float32, W, n, "out_values")), "mrl_eval_spectral_queue")
+        return out
+
+    def eval_pdf_spectral_queue(self, wi, wo, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
+                                n_wavelengths: Optional[int] = None):
+        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
+        W = self._spectral_w(wavelengths, n_wavelengths)
+        val, pdf = (self._zeros(wi, (n, W)), self._zeros(wi, (n,))) if out is None else out
+        self._check(self._lib.mrl_eval_pdf_spectral_queue(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
+            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, _addr(val, np.float32, W, n, "out_values"),
+            _addr(pdf, np.float32, None, n, "out_pdf")), "mrl_eval_pdf_spectral_queue")
+        return val, pdf
+
+    def sample_spectral_queue(self, wi, u, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
+                              n_wavelengths: Optional[int] = None):
+        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
+        W = self._spectral_w(wavelengths, n_wavelengths)
+        wo2, pdf2, w = (self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, W))) if out is None else out
+        self._check(self._lib.mrl_sample_spectral_queue(
+            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
+            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, _addr(wo2, np.float32, 3, n, "out_wo"),
+            _addr(pdf2, np.float32, None, n, "out_pdf"), _addr(w, np.float32, W, n, "out_weight")), "mrl_sample_spectral_queue")
+        return wo2, pdf2, w
 
     def release_material(self, mid: int):
         """Frees the material's device memory; its id becomes a tombstone (batch calls render it as zeros)."""

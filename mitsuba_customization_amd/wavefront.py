@@ -9,7 +9,8 @@ scene — ``eval`` of the light direction and ``sample`` of the continuation dir
 
 Geometry (a sphere on a disc), camera and lights are closed-form torch expressions: plumbing, not the
 product.  ``shade`` is pluggable so the tests can drive the same loop with the CPU oracle and compare
-images; the shipped callers pass :class:`GpuShade`.
+images; the shipped callers pass :class:`GpuShade`.  ``render_spectral`` is the same loop for spectral materials: each path
+carries its own hero wavelengths and each bounce makes one ``mrl_eval_sample_spectral_queue`` call (:class:`GpuSpectralShade`).
 """
 from __future__ import annotations
 
@@ -213,6 +214,129 @@ def render(shade: Callable, width: int, height: int, spp: int = 4, max_depth: in
             d = torch.where(active[:, None], _normalize(to_world(wo2, fs, ft, normal)), d).contiguous()
             o = origin
         image += radiance
+    image /= float(spp)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    stats.total_seconds = time.perf_counter() - t_all
+    return image.reshape(height, width, 3), stats
+
+
+# ---- spectral rendering: hero wavelengths per path (Mitsuba 3's scalar_spectral shape) ----
+WL_MIN, WL_MAX = 360.0, 830.0
+RGB_BANDS = ((WL_MIN, 490.0), (490.0, 590.0), (590.0, WL_MAX))     # blue, green, red box bands: plumbing, not the product
+
+
+def hero_wavelengths(slot: torch.Tensor, sample: int, W: int) -> torch.Tensor:
+    """[n, W] wavelengths of each path: lambda_0 uniform in [360, 830), the others at offsets of 470 / W, wrapped."""
+    span = WL_MAX - WL_MIN
+    l0 = hash_u01(slot * 64 + sample, 9) * span
+    k = torch.arange(W, dtype=torch.float32, device=slot.device) * (span / W)
+    return (WL_MIN + torch.remainder(l0[:, None] + k[None, :], span)).contiguous()
+
+
+def light_spectrum(wl: torch.Tensor) -> torch.Tensor:
+    """The sun: a smooth, slightly warm spectrum around 3."""
+    return 3.0 + 0.3 * (wl - 595.0) / 235.0
+
+
+def sky_spectrum(d: torch.Tensor, wl: torch.Tensor) -> torch.Tensor:
+    """A bluish zenith over a flat horizon; 0.02 below the horizon."""
+    k = torch.clamp(d[:, 2:3], 0.0, 1.0)
+    blue = 0.10 + 0.25 * (WL_MAX - wl) / (WL_MAX - WL_MIN)
+    up = (1.0 - k) * 0.5 + k * blue
+    return torch.where(d[:, 2:3] >= 0.0, up, torch.full_like(up, 0.02))
+
+
+def spectrum_to_rgb(values: torch.Tensor, wl: torch.Tensor) -> torch.Tensor:
+    """[n, W] radiance at the path's wavelengths -> [n, 3] RGB by three box bands (>= 590 R, 490 - 590 G, < 490 B), normalised so
+    that a flat spectrum of 1 gives (1, 1, 1) in expectation over the hero wavelength."""
+    W = wl.shape[1]
+    out = []
+    for lo, hi in reversed(RGB_BANDS):
+        inside = (wl >= lo) & (wl < hi)
+        out.append((values * inside).sum(-1) * ((WL_MAX - WL_MIN) / (W * (hi - lo))))
+    return torch.stack(out, -1)
+
+
+class GpuSpectralShade:
+    """shade() of render_spectral through libmerl_hip: one mrl_eval_sample_spectral_queue call with material ids per bounce, or with
+    partition=True one mrl_partition_by_material and one single-material queue call per material of `materials` (the same bits)."""
+
+    def __init__(self, gpu, partition: bool = False, materials=(0, 1)):
+        self.gpu = gpu
+        self.partition = partition
+        self.materials = tuple(materials)
+        self._out = None
+
+    def __call__(self, wi, wo, u, wl, mat, queue, count):
+        n, W = wi.shape[0], wl.shape[1]
+        if self._out is None or self._out[0].shape != (n, W):
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=wi.device)
+            self._out = (z(n, W), z(n), z(n, 3), z(n), z(n, W))
+        if not self.partition:
+            return self.gpu.eval_sample_spectral_queue(wi, wo, u, wl, queue, count, mat=mat, out=self._out)
+        # the queued slots keep their ids, every other slot is dropped by the partition (id -1)
+        pos = torch.arange(n, dtype=torch.int32, device=wi.device)
+        live = torch.zeros(n, dtype=torch.bool, device=wi.device)
+        live[queue.long()] = pos < count
+        pq, offsets, counts = self.gpu.partition_by_material(torch.where(live, mat, torch.full_like(mat, -1)).contiguous())
+        at = offsets.cpu().tolist()
+        for m in self.materials:
+            self.gpu.eval_sample_spectral_queue(wi, wo, u, wl, pq[at[m]:].contiguous(), counts[m:m + 1], material=m, capacity=n - at[m], out=self._out)
+        return self._out
+
+
+def render_spectral(shade: Callable, width: int, height: int, spp: int = 4, max_depth: int = 4, n_wavelengths: int = 4,
+                    scene: Scene = None, device: str = "cuda:0"):
+    """render() with spectral materials: every path carries n_wavelengths hero wavelengths (hero_wavelengths), beta and radiance are
+    [n, W], the light and the sky are spectra (light_spectrum, sky_spectrum) and the image is binned into RGB (spectrum_to_rgb).
+    shade(wi, wo, u, wl, mat, queue, count) -> (values [n, W], pdf, wo', pdf', weight' [n, W]); only queued slots are read.
+    Returns (image[h, w, 3] as a float32 tensor, Stats)."""
+    scene = scene or Scene()
+    dev = torch.device(device)
+    n, W = width * height, n_wavelengths
+    light = _normalize(_vec(scene.light_dir, dev))[None, :]
+    image = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    slot = torch.arange(n, dtype=torch.int64, device=dev)
+    stats = Stats()
+    t_all = time.perf_counter()
+    for s in range(spp):
+        o, d = camera_rays(scene, width, height, s, dev)
+        wl = hero_wavelengths(slot, s, W)
+        irradiance = light_spectrum(wl)
+        beta = torch.ones((n, W), dtype=torch.float32, device=dev)
+        radiance = torch.zeros((n, W), dtype=torch.float32, device=dev)
+        active = torch.ones(n, dtype=torch.bool, device=dev)
+        for depth in range(max_depth):
+            hit, _, p, normal, mat = intersect(scene, o, d)
+            escaped = active & ~hit
+            radiance = radiance + torch.where(escaped[:, None], beta * sky_spectrum(d, wl), torch.zeros_like(beta))
+            active = active & hit
+            fs, ft = frame(normal)
+            wi = to_local(-d, fs, ft, normal)
+            wld = to_local(light.expand(n, 3), fs, ft, normal)
+            origin = p + scene.eps * normal
+            shadowed, _, _, _, _ = intersect(scene, origin, light.expand(n, 3).contiguous())
+            counter = (slot * 64 + s) * 64 + depth
+            u = torch.stack([hash_u01(counter, 7), hash_u01(counter, 8)], -1).contiguous()
+            queue, count = build_queue(active)
+
+            torch.cuda.synchronize(dev) if dev.type == "cuda" else None
+            t0 = time.perf_counter()
+            values, _, wo2, pdf2, weight = shade(wi, wld, u, wl, mat.contiguous(), queue, count)
+            torch.cuda.synchronize(dev) if dev.type == "cuda" else None
+            dt = time.perf_counter() - t0
+            live = int(count.item())
+            stats.bounces += 1; stats.queued_units += live; stats.shade_seconds += dt
+            stats.per_bounce.append((s, depth, live, dt))
+
+            lit = active & ~shadowed
+            radiance = radiance + torch.where(lit[:, None], beta * values * irradiance, torch.zeros_like(beta))
+            active = active & (pdf2 > 0.0)
+            beta = torch.where(active[:, None], beta * weight, torch.zeros_like(beta))
+            d = torch.where(active[:, None], _normalize(to_world(wo2, fs, ft, normal)), d).contiguous()
+            o = origin
+        image += spectrum_to_rgb(radiance, wl)
     image /= float(spp)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
