@@ -90,6 +90,42 @@ def eval_merl(planar, wi, wo, trilinear=True, center=False, scale=MERL_SCALE):
     return np.where(ok[:, None], v, 0.0)
 
 
+def sampling2d_reference(planar, scale, n_i=32, ks=4, kp=16):
+    """The conditional sampling table P(theta_h | theta_i) of oracle/merl_oracle.c (orc_build_sampling2d) restated: the same
+    quadrature (ks x kp midpoints per theta_h bin, n_i incident bins uniform in cos theta_i), floor and prefix sums, with the angles
+    from half_diff above.  Returns [n_i, 2 n_th + 1]: cdf[n_th + 1] | density[n_th] per incident bin, like
+    OracleTable.sampling2d_arrays."""
+    n = planar.shape[1]
+    q = np.arange(n + 1) / n
+    s = np.sin(q * q * (np.pi / 2)) ** 2; s[n] = 1.0
+    ds = np.diff(s)
+    a = (np.arange(ks) + 0.5) / ks; b = (np.arange(kp) + 0.5) / kp * np.pi
+    S = (s[:-1, None, None] + a[None, :, None] * ds[:, None, None]) + 0 * b[None, None, :]        # [n, ks, kp]
+    PH = np.broadcast_to(b[None, None, :], S.shape)
+    st, ct = np.sqrt(S), np.sqrt(np.maximum(1 - S, 0))
+    h = np.stack([st * np.cos(PH), st * np.sin(PH), ct], -1).reshape(-1, 3)
+    lum_w = np.array([0.2126, 0.7152, 0.0722])
+    out = np.empty((n_i, 2 * n + 1))
+    for i in range(n_i):
+        mu = (i + 0.5) / n_i
+        inn = np.array([np.sqrt(max(1 - mu * mu, 0.0)), 0.0, mu])
+        c = h @ inn
+        o = 2 * c[:, None] * h - inn
+        ok = (c > 0) & (h[:, 2] > 0) & (o[:, 2] > 0)
+        th, td, pd = half_diff(np.broadcast_to(inn, o.shape), o)
+        xh, xd, xp = coords(th, td, pd, planar.shape[1:])
+        rgb = lookup(planar, xh, xd, xp, scale=scale)
+        o_u = o / np.linalg.norm(o, axis=1, keepdims=True)
+        v = np.where(ok, (rgb @ lum_w) * o_u[:, 2] * 4 * c / (2 * h[:, 2]), 0.0)
+        W = ds * v.reshape(n, ks * kp).sum(1) / (ks * kp)
+        total = W.sum(); span = s[n] - s[0]
+        W = W + 0.01 * total * ds / span if total > 0 else ds / span
+        Z = W.sum()
+        out[i, :n + 1] = np.concatenate([[0.0], np.cumsum(W)[:-1] / Z, [1.0]])
+        out[i, n + 1:] = W / (Z * np.pi * ds)
+    return out
+
+
 def eval_standard(planar, wi, wo, full=False, trilinear=True, center=False, scale=MERL_SCALE):
     """The standard parameterisations (include/merl_hip.h enum mrl_param), formulated differently from the oracle:
     theta = arccos(z) of the unit vector, dphi = phi_o - phi_i from the two azimuths, wrapped."""
