@@ -147,6 +147,10 @@ enum mrl_option {
                                   stream; the transfer streams stay unrestricted.  Results do not depend on it.  Verified with hardware
                                   ids: k = 1, 8, 16 idle exactly k CUs; larger masks are dropped by the driver, hence the range
                                   (profiles/r04_cu_mask_probe.json).  Cost on one device: DESIGN.md §7 (profiles/r04_reserved_cus.json). */
+    MRL_OPT_TABLE_GRAD_KERNEL = 16, /* implementation of mrl_table_grad_batch (every value gives the same sums up to f64
+                                  rounding): 0 (default) f64 gradient bricks, lanes of a wave that share a cell merged when many do;
+                                  1 the plain form, every lane adds its values straight into the planar array (the A/B baseline);
+                                  2 bricks, never merged; 3 bricks, always merged. */
     MRL_OPT_MEMORY_LIMIT_MB = 7 /* budget for the context's resident material data (tables + sampling marginals), in MiB;
                                   0 (default) = no budget, the device's free memory is the limit.  An upload that would
                                   exceed the budget — or the device — fails with MRL_ERR_OOM and leaves the context as it
@@ -469,6 +473,35 @@ int mrl_eval_sample_queue(mrl_ctx *ctx, const float *wi, const float *wo, const 
                           const int32_t *mat, int32_t single_id,
                           const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
                           float *out_rgb, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight);
+
+/* ---- fitting tables: the adjoint of eval ----
+ * With MRL_OPT_NEGATIVE at clamp or keep, eval of an RGB table material is linear in the uploaded planar array T: eval(T) = A T,
+ * where row u of A holds, for unit u and channel c, guard x (cos(theta_o), or 1 with MRL_OPT_COSINE_FACTOR = 1) x scale[c] x the
+ * Float corner weights of the trilinear lookup (a single 1 for the nearest lookup), at the coordinates eval itself uses (the
+ * material's parameterisation, MRL_OPT_LOOKUP, MRL_OPT_NODE).  mrl_table_grad_batch computes G += A^T g:
+ *   - the least-squares table of the nearest lookup is A^T y over A^T (A 1) (the normalised splat);
+ *   - eval + this call are what CGLS / gradient descent on |A T - y|^2 need for the trilinear lookup;
+ *   - A^T (dL / d eval) is the table gradient of a differentiable renderer.
+ * grad_planar: [3][n_th][n_td][n_pd] f64 in the layout of mrl_material_upload_table's input, ACCUMULATED into: the caller zeroes it,
+ * a second call adds to the first, and a value no unit reaches keeps its bits.  wi, wo, grad_rgb: [n][3] f32.  A corner on the
+ * padded end of a clamped axis folds onto the last texel, the wrap texel of a periodic azimuth onto texel 0.  A unit that eval
+ * masks (cos(theta_i) <= 0, cos(theta_o) <= 0, a NaN / inf / zero-length direction) contributes nothing, whatever its grad_rgb
+ * holds (NaN and inf included).  id: a live MERL / customized_measurement material that was uploaded or loaded as a planar array (the
+ * call needs its dims, parameterisation and scale — not its texels; a table restored by mrl_material_load_image does not carry
+ * its scale); GGX, n-channel, RGL, spectral, released and unknown ids: MRL_ERR_MATERIAL.  MRL_OPT_NEGATIVE: clamp and keep give
+ * the same result, the adjoint of the blend of the texels as stored — under clamp the derivative with respect to an uploaded
+ * NEGATIVE value is 0, not what this call reports: the caller masks those entries.  Renormalise makes eval non-linear:
+ * MRL_ERR_INVALID.  NULL pointers: MRL_ERR_INVALID; pointers all host or all device (MRL_ERR_POINTER_MIX); n == 0 is MRL_OK and
+ * touches nothing.  Device pointers: asynchronous on the context's stream.  The sums are accumulated with f64 floating-point
+ * atomics (global_atomic_add_f64) into a workspace of 256 B per table cell (373 MB for MERL dims; kept by the context and
+ * reported by mrl_memory_info), then folded into grad_planar: the order of the additions is not fixed, so two runs agree to f64
+ * rounding (~1e-16 of the sum of magnitudes), not bit for bit.  Every call clears and folds the whole workspace, whatever n is
+ * (~0.3 ms for MERL dims): batch the units of a table into few large calls.  The workspace is workspace, not material data: like
+ * the staging and queue buffers it is not counted against MRL_OPT_MEMORY_LIMIT_MB; an allocation that fails is MRL_ERR_OOM.  A
+ * host-pointer call also holds a device copy of grad_planar (24 B per cell) for its duration.
+ * Not offered: material ids per unit, queues, n-channel tables, device groups, the one-unit host path. */
+int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
+                         int32_t id, size_t n, double *grad_planar);
 
 /* ---- synthetic inputs, generated in place on the device; device pointers only ---- */
 int mrl_generate_pairs(mrl_ctx *ctx, uint64_t seed, uint64_t first_index, size_t n,

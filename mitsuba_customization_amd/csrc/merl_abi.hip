@@ -370,6 +370,7 @@ int mrl_destroy(mrl_ctx *ctx)
     }
     if (ctx->d_queues) (void)hipFree(ctx->d_queues);
     if (ctx->d_part_work) (void)hipFree(ctx->d_part_work);
+    if (ctx->d_grad_bricks) (void)hipFree(ctx->d_grad_bricks);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->masked_stream) (void)hipStreamDestroy(ctx->masked_stream);
@@ -414,6 +415,7 @@ int mrl_set_option(mrl_ctx *ctx, int option, int value)
         case MRL_OPT_BLOCK_MAP: if (value < 0 || value > 1) break; ctx->block_map = value; return MRL_OK;
         case MRL_OPT_RGL_SEARCH: if (value < 0 || value > 1) break; ctx->rgl_search = value; return MRL_OK;
         case MRL_OPT_COSINE_FACTOR: if (value < 0 || value > 1) break; ctx->opts.cosine = value; return MRL_OK;
+        case MRL_OPT_TABLE_GRAD_KERNEL: if (value < 0 || value > 3) break; ctx->table_grad_kernel = value; return MRL_OK;
         case MRL_OPT_RESERVED_CUS: {
             // 0 .. 16: the range in which the mask is verified to idle exactly `value` CUs (profiles/r04_cu_mask_probe.json: with 32 or more
             // bits cleared the driver runs the stream on all CUs again)
@@ -474,6 +476,7 @@ int mrl_get_option(const mrl_ctx *ctx, int option, int *value)
         case MRL_OPT_BLOCK_MAP: *value = ctx->block_map; return MRL_OK;
         case MRL_OPT_RGL_SEARCH: *value = ctx->rgl_search; return MRL_OK;
         case MRL_OPT_COSINE_FACTOR: *value = ctx->opts.cosine; return MRL_OK;
+        case MRL_OPT_TABLE_GRAD_KERNEL: *value = ctx->table_grad_kernel; return MRL_OK;
         case MRL_OPT_RESERVED_CUS: *value = ctx->reserved_cus; return MRL_OK;
         case MRL_OPT_NEGATIVE: *value = ctx->opts.negative; return MRL_OK;
         case MRL_OPT_HOST_CHUNK: *value = (int)ctx->host_chunk; return MRL_OK;
@@ -526,7 +529,7 @@ int mrl_memory_info(const mrl_ctx *ctx, size_t *material_bytes, size_t *workspac
     if (workspace_bytes)
         // (the table arena is workspace for as far as no table lives in it: tables placed there are counted as material bytes)
         *workspace_bytes = (ctx->arena_bytes > ctx->arena_used ? ctx->arena_bytes - ctx->arena_used : 0) + ctx->d_stage_bytes + (ctx->queue_cap ? (2 * ctx->queue_cap + 4 * kMaxSegments + 2) * sizeof(uint32_t) : 0) +
-                           ctx->part_work_cap * sizeof(uint32_t) + ctx->d_materials_cap * sizeof(mrl::MaterialDev) +
+                           ctx->part_work_cap * sizeof(uint32_t) + ctx->grad_bricks_cells * 256 + ctx->d_materials_cap * sizeof(mrl::MaterialDev) +
                            (ctx->d_dummy ? 256 + 5 * sizeof(double) : 0);
     if (device_free || device_total) {
         size_t f = 0, t = 0;

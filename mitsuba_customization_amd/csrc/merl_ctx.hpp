@@ -5,6 +5,7 @@
 //   merl_calls.hip         batch, queue and n-channel calls: pointer plumbing, pipelined host arrays, launches
 //   merl_image_cache.hip   on-disk cache of a material's device image
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
+//   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
 #pragma once
 #include "../../include/merl_hip.h"
 
@@ -47,6 +48,10 @@ struct MaterialHost {
     mrl::RglDev rgl{};               // KIND_RGL: the five functions' descriptor (pointers into d_texels)
     bool released = false;           // tombstone left by mrl_material_release; the slot may be reused
     int rows_lookup = 1, rows_node = 0;      // the lookup / node options the conditional sampling rows were integrated under (at upload)
+    // RGB tables uploaded as planar arrays: the channel scales the image was built with (the image itself is pre-scaled).
+    // mrl_table_grad_batch needs them; a table restored from an image file does not carry them (has_scale stays false)
+    double scale[3] = { 1.0, 1.0, 1.0 };
+    bool has_scale = false;
 };
 
 } // namespace mrlabi
@@ -161,6 +166,10 @@ struct mrl_ctx {
     // mrl_partition_by_material: per-chunk count table + totals
     uint32_t *d_part_work = nullptr;
     size_t part_work_cap = 0;
+    // mrl_table_grad_batch: gradient bricks, one 256-B record per table cell (merl_table_grad.hip); grown on demand, reused
+    double *d_grad_bricks = nullptr;
+    size_t grad_bricks_cells = 0;
+    int table_grad_kernel = 0;       // MRL_OPT_TABLE_GRAD_KERNEL
     std::vector<MaterialHost> materials;
     mrl::MaterialDev *d_materials = nullptr;
     size_t d_materials_cap = 0;
@@ -217,6 +226,9 @@ struct mrl_ctx {
 namespace mrlabi {
 
 inline constexpr size_t kMaxSegments = 256 * 8 + 64;     // partition_geometry caps segments at 8 per CU
+
+// ---- merl_calls.hip ----
+int ensure_stage(mrl_ctx *ctx, size_t units, size_t unit_bytes);
 
 // ---- merl_abi.hip ----
 // a non-blocking stream whose kernels may use all but `reserved` of the device's `device_cus` compute units (reserved = 0: a plain

@@ -107,6 +107,8 @@ int upload_table(mrl_ctx *ctx, const double *planar, const int dims[3], const do
     m.dev.layout = layout;
     m.dev.n_ch = 3;
     m.dev.param = param;
+    m.scale[0] = scale[0]; m.scale[1] = scale[1]; m.scale[2] = scale[2];
+    m.has_scale = true;
     {
         // the conditional sampling table, from the table that has just become resident (quadrature + prefix scan on the device)
         const int n_ti = mrl::kSamplingIncidentBins;

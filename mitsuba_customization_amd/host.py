@@ -21,6 +21,7 @@ OPT_TABLE_ARENA_MB = 11
 OPT_RGL_SEARCH = 12           # 0: RGL search tables from LDS when they fit (default), 1: always from memory
 OPT_COSINE_FACTOR = 13        # 0: eval() = f cos(theta_o) (default), 1: eval() = f            
 OPT_RESERVED_CUS = 15          # compute units the batch kernels leave to communication kernels (CU-masked stream)
+OPT_TABLE_GRAD_KERNEL = 16     # table_grad: 0 gradient bricks (default), 1 plain planar atomics (A/B baseline), 2 / 3 bricks never / always merged
 OPT_NEGATIVE = 14             # negative stored values: 0 clamp (default), 1 keep, 2 skip and renormalise   
 NEGATIVE_CLAMP, NEGATIVE_KEEP, NEGATIVE_RENORMALISE = 0, 1, 2
 PARAM_HALF_DIFF, PARAM_STANDARD, PARAM_STANDARD_FULL = 0, 1, 2          # enum mrl_param
@@ -63,6 +64,7 @@ ABI_SYMBOLS = (
     "mrl_group_material_upload_rgl_spectral",
     "mrl_eval_spectral_queue", "mrl_eval_pdf_spectral_queue", "mrl_sample_spectral_queue", "mrl_eval_sample_spectral_queue",
     "mrl_eval_spectral_batch_mat", "mrl_eval_pdf_spectral_batch_mat", "mrl_sample_spectral_batch_mat", "mrl_eval_sample_spectral_batch_mat",
+    "mrl_table_grad_batch",
 )
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
@@ -210,6 +212,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_eval_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp]
     L.mrl_pdf_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp]
     L.mrl_partition_by_material.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
     L.mrl_eval_pdf_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_eval_pdf_queue.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
     L.mrl_sample_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp, fp]
@@ -813,6 +816,30 @@ class MerlHip:
         self._check(self._lib.mrl_eval_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
                                              _addr(mat, np.int32, None, n, "mat"), material, n,
                                              _addr(out, np.float32, 3, n, "out_rgb")), "mrl_eval_batch")
+        return out
+
+    def table_grad(self, wi, wo, grad_rgb, material: int = 0, out=None):
+        """G += A^T grad_rgb, the adjoint of eval in the planar table of an RGB table material (mrl_table_grad_batch) under the
+        context's current options.  Returns f64 [3, n_th, n_td, n_pd]: numpy in -> numpy out, device tensors in -> device tensor
+        out; out= is accumulated into (a fresh result starts from zeros)."""
+        n = int(wi.shape[0]); self._prep(wi)
+        dims = self.material_info(material)[1]
+        shape = (3,) + tuple(int(d) for d in dims)
+        if _is_tensor(wi):
+            import torch
+            if out is None:
+                out = torch.zeros(shape, dtype=torch.float64, device=wi.device)
+            if not _is_tensor(out) or out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != shape:
+                raise ValueError(f"out: need a contiguous torch.float64 tensor of shape {shape}")
+            ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.zeros(shape, dtype=np.float64)
+            if not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.shape != shape:
+                raise ValueError(f"out: need a C-contiguous numpy float64 array of shape {shape}")
+            ptr = out.ctypes.data
+        self._check(self._lib.mrl_table_grad_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                                   _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), material, n, ptr), "mrl_table_grad_batch")
         return out
 
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):

@@ -175,6 +175,21 @@ def make_table(kind: str, seed: int = 0, dims=MERL_DIMS) -> np.ndarray:
 
 
 # ---- MERL .binary file -------------------------------------------------------
+def coherent_pairs(n: int, seed: int = 7, theta_i_deg: float = 30.0, cone_deg: float = 2.0):
+    """A coherent input set: wo uniformly inside a cone of cone_deg around the mirror direction of a fixed wi at theta_i_deg.
+    Returns (wi, wo) as f32 arrays [n, 3]."""
+    rng = np.random.default_rng(seed)
+    ti = np.radians(theta_i_deg)
+    wi = np.tile(np.array([np.sin(ti), 0.0, np.cos(ti)]), (n, 1))
+    axis = np.array([-np.sin(ti), 0.0, np.cos(ti)])
+    cos_t = 1.0 - rng.random(n) * (1.0 - np.cos(np.radians(cone_deg)))
+    sin_t = np.sqrt(np.maximum(1.0 - cos_t * cos_t, 0.0))
+    phi = rng.random(n) * 2 * np.pi
+    e1 = np.array([np.cos(ti), 0.0, np.sin(ti)]); e2 = np.array([0.0, 1.0, 0.0])
+    wo = cos_t[:, None] * axis + (sin_t * np.cos(phi))[:, None] * e1 + (sin_t * np.sin(phi))[:, None] * e2
+    return wi.astype(np.float32), wo.astype(np.float32)
+
+
 def write_merl_binary(path: str, planar: np.ndarray) -> None:
     planar = np.ascontiguousarray(planar, dtype="<f8")
     assert planar.ndim == 4 and planar.shape[0] == 3
