@@ -46,16 +46,27 @@ int pointer_kind(const void *p)
 }
 
 // all non-null pointers must be of one kind; returns 0/1, or -1 on a mix
-int common_kind(std::initializer_list<const void *> ptrs)
+int common_kind(std::initializer_list<const void *> ptrs, const StreamList &streams)
 {
+    std::vector<const void *> all(ptrs);
+    for (const HostStream &s : streams) all.push_back(s.ptr);
     int kind = -2;
-    for (const void *p : ptrs) {
+    for (const void *p : all) {
         if (!p) continue;
         int k = pointer_kind(p);
         if (kind == -2) kind = k;
         else if (kind != k) return -1;
     }
     return kind == -2 ? 1 : kind;
+}
+
+int DeviceBuf::reserve(mrl_ctx *ctx, size_t need)
+{
+    if (need <= bytes) return MRL_OK;
+    if (p) { MRL_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(p); p = nullptr; bytes = 0; }
+    MRL_ALLOC(ctx, hipMalloc(&p, need));
+    bytes = need;
+    return MRL_OK;
 }
 
 int sync_material_array(mrl_ctx *ctx)
@@ -362,15 +373,12 @@ int mrl_destroy(mrl_ctx *ctx)
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->d_materials) (void)hipFree(ctx->d_materials);
     if (ctx->d_dummy) (void)hipFree(ctx->d_dummy);
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+    for (DeviceBuf &b : ctx->buf) if (b.p) (void)hipFree(b.p);
     ctx->pipe.pool.stop();
     for (int s = 0; s < 2; ++s) {
         if (ctx->pipe.pin[s]) (void)hipHostFree(ctx->pipe.pin[s]);
         if (ctx->pipe.done[s]) (void)hipEventDestroy(ctx->pipe.done[s]);
     }
-    if (ctx->d_queues) (void)hipFree(ctx->d_queues);
-    if (ctx->d_part_work) (void)hipFree(ctx->d_part_work);
-    if (ctx->d_grad_bricks) (void)hipFree(ctx->d_grad_bricks);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->masked_stream) (void)hipStreamDestroy(ctx->masked_stream);
@@ -526,11 +534,12 @@ int mrl_memory_info(const mrl_ctx *ctx, size_t *material_bytes, size_t *workspac
     if (!ctx) return MRL_ERR_INVALID;
     MRL_GUARD(ctx);
     if (material_bytes) *material_bytes = ctx->material_bytes;
-    if (workspace_bytes)
+    if (workspace_bytes) {
         // (the table arena is workspace for as far as no table lives in it: tables placed there are counted as material bytes)
-        *workspace_bytes = (ctx->arena_bytes > ctx->arena_used ? ctx->arena_bytes - ctx->arena_used : 0) + ctx->d_stage_bytes + (ctx->queue_cap ? (2 * ctx->queue_cap + 4 * kMaxSegments + 2) * sizeof(uint32_t) : 0) +
-                           ctx->part_work_cap * sizeof(uint32_t) + ctx->grad_bricks_cells * 256 + ctx->d_materials_cap * sizeof(mrl::MaterialDev) +
+        *workspace_bytes = (ctx->arena_bytes > ctx->arena_used ? ctx->arena_bytes - ctx->arena_used : 0) + ctx->d_materials_cap * sizeof(mrl::MaterialDev) +
                            (ctx->d_dummy ? 256 + 5 * sizeof(double) : 0);
+        for (const DeviceBuf &b : ctx->buf) *workspace_bytes += b.bytes;
+    }
     if (device_free || device_total) {
         size_t f = 0, t = 0;
         if (hipSetDevice(ctx->device) != hipSuccess || hipMemGetInfo(&f, &t) != hipSuccess) { (void)hipGetLastError(); return MRL_ERR_HIP; }

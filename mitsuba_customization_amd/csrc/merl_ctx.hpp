@@ -2,7 +2,8 @@
 // error / lock macros and the internal functions one file defines and another calls.  Not installed; nothing here is part of the ABI.
 //   merl_abi.hip           contexts, options, streams, memory helpers, one-unit call service, errors
 //   merl_materials.hip     material constructors (MERL / customized_measurement / n-channel / GGX / RGL), release, host images
-//   merl_calls.hip         batch, queue and n-channel calls: pointer plumbing, pipelined host arrays, launches
+//   merl_calls.hip         batch, queue and n-channel calls: a call's arrays as a stream list, the two host-array movers, launches
+//   merl_host_stage.hpp    host-array path, host C++ only: stream list, slot layout, the chunk loop, the copy threads
 //   merl_image_cache.hip   on-disk cache of a material's device image
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
 //   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
@@ -31,6 +32,7 @@
 #include "merl_image_file.hpp"
 #include "merl_scalar_host.hpp"
 #include "merl_host_table.hpp"
+#include "merl_host_stage.hpp"
 
 namespace mrlabi {
 
@@ -54,83 +56,25 @@ struct MaterialHost {
     bool has_scale = false;
 };
 
-} // namespace mrlabi
-using mrlabi::MaterialHost;
-
-
-// ---- pipelined host-array path -------------------------------------------------------------------------------------
-// A host that holds plain (pageable) arrays — what a CPU renderer hands over — used to be staged with hipMemcpyAsync,
-// which the runtime serialises through one bounce buffer at ~11 GB/s (140-150 M units/s).  Instead: a few copy threads
-// move chunk c+1 of the caller's arrays into pinned, device-mapped buffers and chunk c-1 of the results out of them,
-// while the kernel of chunk c reads and writes the pinned buffers over PCIe itself (zero copy, no staging in HBM).
-struct CopyPool {
-    struct Seg { void *dst; const void *src; size_t bytes; };
-    std::vector<std::thread> workers;
-    std::mutex mu;
-    std::condition_variable wake, done;
-    std::vector<Seg> segs;
-    size_t next = 0, finished = 0;
-    uint64_t generation = 0;
-    bool quit = false;
-
-    void start(int n)
-    {
-        for (int t = 0; t < n; ++t)
-            workers.emplace_back([this]() {
-                uint64_t seen = 0;
-                for (;;) {
-                    std::unique_lock<std::mutex> lk(mu);
-                    wake.wait(lk, [&]() { return quit || (generation != seen && next < segs.size()) || (generation != seen && segs.empty()); });
-                    if (quit) return;
-                    if (next >= segs.size()) { seen = generation; continue; }
-                    while (next < segs.size()) {
-                        const Seg sg = segs[next++];
-                        lk.unlock();
-                        std::memcpy(sg.dst, sg.src, sg.bytes);
-                        lk.lock();
-                        if (++finished == segs.size()) done.notify_all();
-                    }
-                    seen = generation;
-                }
-            });
-    }
-    // copies every segment, split into slices so that all workers (and the caller) share the work; returns when done
-    void run(const std::vector<Seg> &whole)
-    {
-        constexpr size_t kSlice = (size_t)2 << 20;
-        std::vector<Seg> sliced;
-        for (const Seg &w : whole)
-            for (size_t off = 0; off < w.bytes; off += kSlice)
-                sliced.push_back({ (char *)w.dst + off, (const char *)w.src + off, std::min(kSlice, w.bytes - off) });
-        if (sliced.empty()) return;
-        if (workers.empty()) { for (const Seg &sg : sliced) std::memcpy(sg.dst, sg.src, sg.bytes); return; }
-        std::unique_lock<std::mutex> lk(mu);
-        segs = std::move(sliced); next = 0; finished = 0; ++generation;
-        wake.notify_all();
-        while (next < segs.size()) {                              // the caller copies too
-            const Seg sg = segs[next++];
-            lk.unlock();
-            std::memcpy(sg.dst, sg.src, sg.bytes);
-            lk.lock();
-            ++finished;
-        }
-        done.wait(lk, [&]() { return finished == segs.size(); });
-        segs.clear();
-    }
-    void stop()
-    {
-        { std::lock_guard<std::mutex> lk(mu); quit = true; }
-        wake.notify_all();
-        for (auto &t : workers) t.join();
-        workers.clear();
-    }
+// a device buffer that only grows
+struct DeviceBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    // at least `need` bytes: as it is, or (after the context's stream has drained) freed and allocated anew; contents are not kept
+    int reserve(mrl_ctx *ctx, size_t need);
 };
 
+} // namespace mrlabi
+using mrlabi::MaterialHost;
+using mrlabi::DeviceBuf;
+
+
+// the pipelined mover's state (merl_calls.hip): two pinned, device-mapped slots (slot_layout), an event per slot, the copy threads
 struct HostPipe {
-    char *pin[2] = { nullptr, nullptr };             // per slot: inputs then outputs of one chunk
+    char *pin[2] = { nullptr, nullptr };
     size_t slot_bytes = 0;
     hipEvent_t done[2] = { nullptr, nullptr };
-    CopyPool pool;
+    mrlabi::CopyPool pool;
     int threads = -1;                                // workers the pool was started with
 };
 
@@ -160,15 +104,13 @@ struct mrl_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // kind-partitioned mixed batches: [2][queue_cap] unit indices + partition work area behind them
-    uint32_t *d_queues = nullptr;
-    size_t queue_cap = 0;
-    // mrl_partition_by_material: per-chunk count table + totals
-    uint32_t *d_part_work = nullptr;
-    size_t part_work_cap = 0;
-    // mrl_table_grad_batch: gradient bricks, one 256-B record per table cell (merl_table_grad.hip); grown on demand, reused
-    double *d_grad_bricks = nullptr;
-    size_t grad_bricks_cells = 0;
+    // the grow-only workspaces (freed by mrl_destroy, summed by mrl_memory_info):
+    //   BUF_STAGE        one slot of a staged host-array call (slot_layout)
+    //   BUF_QUEUES       kind-partitioned mixed batches: [2][n] unit indices + partition work area behind them
+    //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
+    //   BUF_GRAD_BRICKS  mrl_table_grad_batch: gradient bricks, one 256-B record per table cell (merl_table_grad.hip)
+    enum { BUF_STAGE, BUF_QUEUES, BUF_PART_WORK, BUF_GRAD_BRICKS, BUF_COUNT };
+    DeviceBuf buf[BUF_COUNT];
     int table_grad_kernel = 0;       // MRL_OPT_TABLE_GRAD_KERNEL
     std::vector<MaterialHost> materials;
     mrl::MaterialDev *d_materials = nullptr;
@@ -189,8 +131,6 @@ struct mrl_ctx {
     hipStream_t masked_stream = nullptr;     // own stream restricted to the unreserved CUs (created by MRL_OPT_RESERVED_CUS > 0)
     int host_threads = 4;            // MRL_OPT_HOST_THREADS: copy threads of the pipelined host-array path; 0 = staged hipMemcpy path
     HostPipe pipe;
-    void *d_stage = nullptr;
-    size_t d_stage_bytes = 0;
     ScalarDevice scalar_dev;
     std::atomic<ScalarSvc *> scalar{ nullptr };      // created by the first mrl_scalar_eval_sample
     // MRL_OPT_TABLE_ARENA_MB: one device allocation that RGB tables are placed in back to back (2 MiB aligned)
@@ -228,7 +168,23 @@ namespace mrlabi {
 inline constexpr size_t kMaxSegments = 256 * 8 + 64;     // partition_geometry caps segments at 8 per CU
 
 // ---- merl_calls.hip ----
-int ensure_stage(mrl_ctx *ctx, size_t units, size_t unit_bytes);
+// A whole-array call, host or device pointers: the RGB and n-channel entry points, and (wl / n_ch = W) the spectral ones
+struct BatchCall {
+    int mode;                                    // a mrl::Mode
+    const float *wi, *wo, *u;
+    const int32_t *mat;
+    int32_t single_id;
+    size_t n;
+    float *out_rgb, *out_pdf, *out_wo, *out_pdf2, *out_weight;
+    int n_ch = 0;                                // values per unit in out_rgb / out_weight.  0: three, the RGB entry points; > 0: *_nch and spectral calls
+    const float *wl = nullptr;                   // spectral calls: n_ch wavelengths per unit, or NULL for the file's own nodes
+};
+StreamList streams_of(const BatchCall &c);                                   // the arrays a call of this mode touches
+BatchCall on_slot(BatchCall c, char *const *addr, size_t m);                 // the same call on m units at one address per listed stream
+mrl::BatchArgs batch_args(const mrl_ctx *ctx, const BatchCall &c);           // streams, materials, n_materials, opts; the rest zero
+using HostLaunch = std::function<int(char *const *addr, size_t m)>;
+// host arrays through the context's stage buffer, one chunk at a time (cap_bytes > 0: chunks so small that the slot stays below it)
+int run_host_staged(mrl_ctx *ctx, const StreamList &streams, size_t n, size_t cap_bytes, const HostLaunch &launch);
 
 // ---- merl_abi.hip ----
 // a non-blocking stream whose kernels may use all but `reserved` of the device's `device_cus` compute units (reserved = 0: a plain
@@ -237,7 +193,7 @@ int ensure_stage(mrl_ctx *ctx, size_t units, size_t unit_bytes);
 hipError_t create_compute_stream(int device_cus, int reserved, hipStream_t *out);
 int fail(mrl_ctx *ctx, int status, const std::string &msg);
 int pointer_kind(const void *p);                                  // 1 = the device can dereference it, 0 = plain host
-int common_kind(std::initializer_list<const void *> ptrs);        // 0 / 1, or -1 on a mix
+int common_kind(std::initializer_list<const void *> ptrs, const StreamList &streams = {});    // 0 / 1, or -1 on a mix
 int sync_material_array(mrl_ctx *ctx);
 int ensure_dummy(mrl_ctx *ctx);
 mrl::MaterialDev tombstone_dev(const mrl_ctx *ctx);

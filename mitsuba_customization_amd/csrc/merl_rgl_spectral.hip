@@ -13,108 +13,54 @@ using namespace mrlabi;
 
 namespace {
 
-struct SpectralCall {
-    int mode;                                        // a mrl::Mode other than MODE_PDF (the RGB pdf call serves these materials)
-    const float *wi, *wo, *u, *wl;
-    int W;
-    int32_t id;
-    size_t n;                                        // units; the queue form: the capacity of the slot arrays
-    float *out_values, *out_pdf, *out_wo, *out_pdf2, *out_weight;
-    const int32_t *mat = nullptr;                    // a material id per unit (id is then unused)
-    bool queued = false;                             // the queue form: units queue[0 .. min(*queue_count, n))
-    const uint32_t *queue = nullptr, *queue_count = nullptr;
-};
+// a spectral call: W values per unit at the wavelengths wl [n][W] (NULL: the file's own nodes).  Any mode but MODE_PDF (the RGB pdf call
+// serves these materials); n is the number of units, in the queue form the capacity of the slot arrays
+BatchCall spectral(BatchCall c, const float *wl, int W)
+{
+    c.wl = wl; c.n_ch = W;
+    return c;
+}
 
 // checks and launches the three forms: whole arrays of one material (mrl_*_spectral_batch), whole arrays with ids (*_spectral_batch_mat),
-// a wavefront queue with or without ids (*_spectral_queue)
-int run_spectral(mrl_ctx *ctx, const SpectralCall &c)
+// a wavefront queue with or without ids (*_spectral_queue: units queue[0 .. min(*queue_count, n)))
+int run_spectral(mrl_ctx *ctx, const BatchCall &c, bool queued = false, const uint32_t *queue = nullptr, const uint32_t *queue_count = nullptr)
 {
     if (!ctx) return MRL_ERR_INVALID;
     MRL_GUARD(ctx);
-    const bool has_eval = mrl::mode_eval(c.mode), has_pdf = mrl::mode_pdf(c.mode), has_sample = mrl::mode_sample(c.mode);
     if (c.n == 0) return MRL_OK;
-    if (!c.wi || (has_eval && (!c.wo || !c.out_values)) || (has_pdf && !c.out_pdf) || (has_sample && (!c.u || !c.out_wo || !c.out_pdf2 || !c.out_weight)))
-        return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    if (c.queued && (!c.queue || !c.queue_count)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    if (c.queued && c.n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
+    const int W = c.n_ch;
+    const StreamList streams = streams_of(c);
+    if (first_null(streams) || (queued && (!queue || !queue_count))) return fail(ctx, MRL_ERR_INVALID, "null array argument");
+    if (queued && c.n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
     const MaterialHost *single = nullptr;
     if (c.mat) {
         // the materials of one call may have different wavelength grids: "the file's own nodes" names no one set of wavelengths
         if (!c.wl) return fail(ctx, MRL_ERR_INVALID, "a call with material ids needs per-unit wavelengths");
-        if (c.W < 1 || c.W > 4096) return fail(ctx, MRL_ERR_INVALID, "1..4096 wavelengths per unit");
+        if (W < 1 || W > 4096) return fail(ctx, MRL_ERR_INVALID, "1..4096 wavelengths per unit");
     } else {
-        if (c.id < 0 || (size_t)c.id >= ctx->materials.size() || ctx->materials[(size_t)c.id].released) return fail(ctx, MRL_ERR_MATERIAL, "unknown material id");
-        single = &ctx->materials[(size_t)c.id];
+        if (c.single_id < 0 || (size_t)c.single_id >= ctx->materials.size() || ctx->materials[(size_t)c.single_id].released) return fail(ctx, MRL_ERR_MATERIAL, "unknown material id");
+        single = &ctx->materials[(size_t)c.single_id];
         if (single->dev.kind != mrl::KIND_RGL_SPECTRAL)
             return fail(ctx, MRL_ERR_MATERIAL, "the spectral entry points evaluate spectral RGL materials (mrl_material_upload_rgl_spectral)");
-        if (c.W < 1 || c.W > 4096) return fail(ctx, MRL_ERR_INVALID, "1..4096 wavelengths per unit");
-        if (!c.wl && c.W != single->rgl.n_wl)
+        if (W < 1 || W > 4096) return fail(ctx, MRL_ERR_INVALID, "1..4096 wavelengths per unit");
+        if (!c.wl && W != single->rgl.n_wl)
             return fail(ctx, MRL_ERR_INVALID, "without a wavelength array the values are those at the file's " + std::to_string(single->rgl.n_wl) + " wavelength nodes");
     }
     MRL_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = common_kind({ c.wi, has_eval ? c.wo : nullptr, has_sample ? c.u : nullptr, c.wl, c.mat, has_eval ? c.out_values : nullptr, has_pdf ? c.out_pdf : nullptr,
-                                   has_sample ? c.out_wo : nullptr, has_sample ? c.out_pdf2 : nullptr, has_sample ? c.out_weight : nullptr, c.queue, c.queue_count });
-    if (c.queued && kind != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
+    const int kind = common_kind({ queue, queue_count }, streams);
+    if (queued && kind != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
     if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
-    auto launch = [&](const float *wi, const float *wo, const float *u, const float *wl, const int32_t *mat, size_t n, float *values, float *pdf, float *wo2,
-                      float *pdf2, float *w) {
-        mrl::BatchArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.wi = wi; a.wo = wo; a.u = u; a.mat = mat; a.n = n;
-        a.out_rgb = values; a.out_pdf = pdf; a.out_wo = wo2; a.out_pdf2 = pdf2; a.out_weight = w;
-        a.opts = ctx->opts;
-        if (!c.mat && !c.queued) return mrl::launch_rgl_spectral(c.mode, a, single->rgl, wl, c.W, ctx->rgl_search, ctx->compute_units, ctx->stream);
-        a.materials = ctx->d_materials;
-        a.n_materials = (int)ctx->materials.size();
-        a.idx = c.queue; a.idx_count = c.queue_count;
-        return mrl::launch_rgl_spectral_q(c.mode, a, single ? &single->rgl : nullptr, c.queued, wl, c.W, ctx->rgl_search, ctx->compute_units, ctx->stream);
-    };
-    if (kind == 1) {
-        MRL_HIP(ctx, launch(c.wi, c.wo, c.u, c.wl, c.mat, c.n, c.out_values, c.out_pdf, c.out_wo, c.out_pdf2, c.out_weight));
+    auto launch = [&](const BatchCall &d) -> int {
+        mrl::BatchArgs a = batch_args(ctx, d);
+        a.idx = queue; a.idx_count = queue_count;
+        if (!d.mat && !queued) MRL_HIP(ctx, mrl::launch_rgl_spectral(d.mode, a, single->rgl, d.wl, W, ctx->rgl_search, ctx->compute_units, ctx->stream));
+        else MRL_HIP(ctx, mrl::launch_rgl_spectral_q(d.mode, a, single ? &single->rgl : nullptr, queued, d.wl, W, ctx->rgl_search, ctx->compute_units, ctx->stream));
         return MRL_OK;
-    }
-    // host arrays: staged through HBM in chunks (a renderer that holds spectral rays on the host hands over a few million at a time)
-    const size_t W = (size_t)c.W;
-    const size_t unit_floats = 3 + 3 + 2 + W + W + 1 + 3 + 1 + W + 1;
-    const size_t chunk = std::min(c.n, std::max<size_t>(1, std::min(ctx->host_chunk, ((size_t)256 << 20) / (unit_floats * 4))));
-    float *d = nullptr;
-    MRL_ALLOC(ctx, hipMalloc((void **)&d, chunk * unit_floats * sizeof(float)));
-    float *d_wi = d, *d_wo = d_wi + 3 * chunk, *d_u = d_wo + 3 * chunk, *d_wl = d_u + 2 * chunk, *d_val = d_wl + W * chunk, *d_pdf = d_val + W * chunk,
-          *d_wo2 = d_pdf + chunk, *d_pdf2 = d_wo2 + 3 * chunk, *d_w = d_pdf2 + chunk;
-    int32_t *d_mat = (int32_t *)(d_w + W * chunk);
-    hipError_t e = hipSuccess;
-    for (size_t off = 0; off < c.n && e == hipSuccess; off += chunk) {
-        const size_t m = std::min(chunk, c.n - off);
-        e = hipMemcpyAsync(d_wi, c.wi + 3 * off, 12 * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && has_eval) e = hipMemcpyAsync(d_wo, c.wo + 3 * off, 12 * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && has_sample) e = hipMemcpyAsync(d_u, c.u + 2 * off, 8 * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && c.wl) e = hipMemcpyAsync(d_wl, c.wl + W * off, 4 * W * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && c.mat) e = hipMemcpyAsync(d_mat, c.mat + off, 4 * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = launch(d_wi, d_wo, d_u, c.wl ? d_wl : nullptr, c.mat ? d_mat : nullptr, m, d_val, d_pdf, d_wo2, d_pdf2, d_w);
-        if (e == hipSuccess && has_eval) e = hipMemcpyAsync(c.out_values + W * off, d_val, 4 * W * m, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && has_pdf) e = hipMemcpyAsync(c.out_pdf + off, d_pdf, 4 * m, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && has_sample) {
-            e = hipMemcpyAsync(c.out_wo + 3 * off, d_wo2, 12 * m, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(c.out_pdf2 + off, d_pdf2, 4 * m, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(c.out_weight + W * off, d_w, 4 * W * m, hipMemcpyDeviceToHost, ctx->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(d);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, MRL_ERR_HIP, std::string("spectral call: ") + hipGetErrorString(e)); }
-    return MRL_OK;
-}
-
-SpectralCall queue_call(SpectralCall c, const int32_t *mat, const uint32_t *queue, const uint32_t *queue_count)
-{
-    c.mat = mat; c.queued = true; c.queue = queue; c.queue_count = queue_count;
-    return c;
-}
-
-SpectralCall mat_call(SpectralCall c, const int32_t *mat)
-{
-    c.mat = mat;
-    return c;
+    };
+    if (kind == 1) return launch(c);
+    // host arrays: staged through HBM in chunks of at most 256 MiB of slot (W may be 4096; a renderer that holds spectral rays on the host
+    // hands over a few million at a time)
+    return run_host_staged(ctx, streams, c.n, (size_t)256 << 20, [&](char *const *addr, size_t m) { return launch(on_slot(c, addr, m)); });
 }
 
 } // namespace
@@ -123,71 +69,71 @@ extern "C" {
 
 int mrl_eval_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, int32_t id, size_t n, float *out_values)
 {
-    return run_spectral(ctx, { mrl::MODE_EVAL, wi, wo, nullptr, wavelengths, n_wavelengths, id, n, out_values, nullptr, nullptr, nullptr, nullptr });
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL, wi, wo, nullptr, nullptr, id, n, out_values, nullptr, nullptr, nullptr, nullptr }, wavelengths, n_wavelengths));
 }
 int mrl_eval_pdf_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, int32_t id, size_t n,
                                 float *out_values, float *out_pdf)
 {
-    return run_spectral(ctx, { mrl::MODE_EVAL_PDF, wi, wo, nullptr, wavelengths, n_wavelengths, id, n, out_values, out_pdf, nullptr, nullptr, nullptr });
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL_PDF, wi, wo, nullptr, nullptr, id, n, out_values, out_pdf, nullptr, nullptr, nullptr }, wavelengths, n_wavelengths));
 }
 int mrl_sample_spectral_batch(mrl_ctx *ctx, const float *wi, const float *u, const float *wavelengths, int n_wavelengths, int32_t id, size_t n,
                               float *out_wo, float *out_pdf, float *out_weight)
 {
-    return run_spectral(ctx, { mrl::MODE_SAMPLE, wi, nullptr, u, wavelengths, n_wavelengths, id, n, nullptr, nullptr, out_wo, out_pdf, out_weight });
+    return run_spectral(ctx, spectral({ mrl::MODE_SAMPLE, wi, nullptr, u, nullptr, id, n, nullptr, nullptr, out_wo, out_pdf, out_weight }, wavelengths, n_wavelengths));
 }
 int mrl_eval_sample_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths, int32_t id,
                                    size_t n, float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    return run_spectral(ctx, { mrl::MODE_EVAL_SAMPLE, wi, wo, u, wavelengths, n_wavelengths, id, n, out_values, out_pdf, out_wo, out_pdf2, out_weight });
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL_SAMPLE, wi, wo, u, nullptr, id, n, out_values, out_pdf, out_wo, out_pdf2, out_weight }, wavelengths, n_wavelengths));
 }
 
 // ---- over a wavefront queue (device pointers; mat == NULL: the material single_id) ----
 int mrl_eval_spectral_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, const int32_t *mat, int32_t single_id,
                             const uint32_t *queue, const uint32_t *queue_count, size_t capacity, float *out_values)
 {
-    return run_spectral(ctx, queue_call({ mrl::MODE_EVAL, wi, wo, nullptr, wavelengths, n_wavelengths, single_id, capacity, out_values, nullptr, nullptr, nullptr, nullptr },
-                                        mat, queue, queue_count));
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL, wi, wo, nullptr, mat, single_id, capacity, out_values, nullptr, nullptr, nullptr, nullptr }, wavelengths, n_wavelengths),
+                        true, queue, queue_count);
 }
 int mrl_eval_pdf_spectral_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, const int32_t *mat, int32_t single_id,
                                 const uint32_t *queue, const uint32_t *queue_count, size_t capacity, float *out_values, float *out_pdf)
 {
-    return run_spectral(ctx, queue_call({ mrl::MODE_EVAL_PDF, wi, wo, nullptr, wavelengths, n_wavelengths, single_id, capacity, out_values, out_pdf, nullptr, nullptr, nullptr },
-                                        mat, queue, queue_count));
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL_PDF, wi, wo, nullptr, mat, single_id, capacity, out_values, out_pdf, nullptr, nullptr, nullptr }, wavelengths, n_wavelengths),
+                        true, queue, queue_count);
 }
 int mrl_sample_spectral_queue(mrl_ctx *ctx, const float *wi, const float *u, const float *wavelengths, int n_wavelengths, const int32_t *mat, int32_t single_id,
                               const uint32_t *queue, const uint32_t *queue_count, size_t capacity, float *out_wo, float *out_pdf, float *out_weight)
 {
-    return run_spectral(ctx, queue_call({ mrl::MODE_SAMPLE, wi, nullptr, u, wavelengths, n_wavelengths, single_id, capacity, nullptr, nullptr, out_wo, out_pdf, out_weight },
-                                        mat, queue, queue_count));
+    return run_spectral(ctx, spectral({ mrl::MODE_SAMPLE, wi, nullptr, u, mat, single_id, capacity, nullptr, nullptr, out_wo, out_pdf, out_weight }, wavelengths, n_wavelengths),
+                        true, queue, queue_count);
 }
 int mrl_eval_sample_spectral_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths, const int32_t *mat,
                                    int32_t single_id, const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
                                    float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    return run_spectral(ctx, queue_call({ mrl::MODE_EVAL_SAMPLE, wi, wo, u, wavelengths, n_wavelengths, single_id, capacity, out_values, out_pdf, out_wo, out_pdf2, out_weight },
-                                        mat, queue, queue_count));
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, single_id, capacity, out_values, out_pdf, out_wo, out_pdf2, out_weight }, wavelengths, n_wavelengths),
+                        true, queue, queue_count);
 }
 
 // ---- whole arrays with a material id per unit (host or device pointers) ----
 int mrl_eval_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, const int32_t *mat, size_t n,
                                 float *out_values)
 {
-    return run_spectral(ctx, mat_call({ mrl::MODE_EVAL, wi, wo, nullptr, wavelengths, n_wavelengths, -1, n, out_values, nullptr, nullptr, nullptr, nullptr }, mat));
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL, wi, wo, nullptr, mat, -1, n, out_values, nullptr, nullptr, nullptr, nullptr }, wavelengths, n_wavelengths));
 }
 int mrl_eval_pdf_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *wavelengths, int n_wavelengths, const int32_t *mat, size_t n,
                                     float *out_values, float *out_pdf)
 {
-    return run_spectral(ctx, mat_call({ mrl::MODE_EVAL_PDF, wi, wo, nullptr, wavelengths, n_wavelengths, -1, n, out_values, out_pdf, nullptr, nullptr, nullptr }, mat));
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL_PDF, wi, wo, nullptr, mat, -1, n, out_values, out_pdf, nullptr, nullptr, nullptr }, wavelengths, n_wavelengths));
 }
 int mrl_sample_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *u, const float *wavelengths, int n_wavelengths, const int32_t *mat, size_t n,
                                   float *out_wo, float *out_pdf, float *out_weight)
 {
-    return run_spectral(ctx, mat_call({ mrl::MODE_SAMPLE, wi, nullptr, u, wavelengths, n_wavelengths, -1, n, nullptr, nullptr, out_wo, out_pdf, out_weight }, mat));
+    return run_spectral(ctx, spectral({ mrl::MODE_SAMPLE, wi, nullptr, u, mat, -1, n, nullptr, nullptr, out_wo, out_pdf, out_weight }, wavelengths, n_wavelengths));
 }
 int mrl_eval_sample_spectral_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *u, const float *wavelengths, int n_wavelengths, const int32_t *mat,
                                        size_t n, float *out_values, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
-    return run_spectral(ctx, mat_call({ mrl::MODE_EVAL_SAMPLE, wi, wo, u, wavelengths, n_wavelengths, -1, n, out_values, out_pdf, out_wo, out_pdf2, out_weight }, mat));
+    return run_spectral(ctx, spectral({ mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, -1, n, out_values, out_pdf, out_wo, out_pdf2, out_weight }, wavelengths, n_wavelengths));
 }
 
 int mrl_material_wavelengths(mrl_ctx *ctx, int id, int *n_wavelengths, float *out, size_t max_floats)

@@ -248,23 +248,6 @@ hipError_t launch_table_grad_fold(const double *bricks, double *planar, const in
 
 using namespace mrlabi;
 
-namespace {
-
-int ensure_grad_bricks(mrl_ctx *ctx, size_t cells)
-{
-    if (cells <= ctx->grad_bricks_cells) return MRL_OK;
-    if (ctx->d_grad_bricks) {
-        MRL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_grad_bricks);
-        ctx->d_grad_bricks = nullptr; ctx->grad_bricks_cells = 0;
-    }
-    MRL_ALLOC(ctx, hipMalloc((void **)&ctx->d_grad_bricks, cells * mrl::kBrickSlots * sizeof(double)));
-    ctx->grad_bricks_cells = cells;
-    return MRL_OK;
-}
-
-} // namespace
-
 extern "C" {
 
 int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, int32_t id, size_t n, double *grad_planar)
@@ -272,7 +255,8 @@ int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const f
     if (!ctx) return MRL_ERR_INVALID;
     MRL_GUARD(ctx);
     if (n == 0) return MRL_OK;
-    if (!wi || !wo || !grad_rgb || !grad_planar) return fail(ctx, MRL_ERR_INVALID, "null array argument");
+    const StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
+    if (first_null(streams) || !grad_planar) return fail(ctx, MRL_ERR_INVALID, "null array argument");
     if (id < 0 || (size_t)id >= ctx->materials.size() || ctx->materials[(size_t)id].released) return fail(ctx, MRL_ERR_MATERIAL, "unknown material id");
     const MaterialHost &mh = ctx->materials[(size_t)id];
     if (mh.dev.kind != mrl::KIND_MERL && mh.dev.kind != mrl::KIND_TABLE)
@@ -281,7 +265,7 @@ int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const f
     if (ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
         return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise makes eval non-linear in the table: no adjoint");
     MRL_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = common_kind({ wi, wo, grad_rgb, grad_planar });
+    const int kind = common_kind({ grad_planar }, streams);
     if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
 
     const int dims[3] = { mh.dev.n_th, mh.dev.n_td, mh.dev.n_pd };
@@ -293,9 +277,10 @@ int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const f
     a.opts = ctx->opts;
     a.scale[0] = mh.scale[0]; a.scale[1] = mh.scale[1]; a.scale[2] = mh.scale[2];
     if (variant != 1) {
-        const int rc = ensure_grad_bricks(ctx, plane);
+        DeviceBuf &bricks = ctx->buf[mrl_ctx::BUF_GRAD_BRICKS];      // one 256-B record per table cell; grown on demand, reused
+        const int rc = bricks.reserve(ctx, plane * mrl::kBrickSlots * sizeof(double));
         if (rc != MRL_OK) return rc;
-        a.bricks = ctx->d_grad_bricks;
+        a.bricks = (double *)bricks.p;
         MRL_HIP(ctx, hipMemsetAsync(a.bricks, 0, plane * mrl::kBrickSlots * sizeof(double), ctx->stream));
     }
     if (kind == 1) {
@@ -309,20 +294,13 @@ int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const f
     MRL_ALLOC(ctx, hipMalloc((void **)&d_planar, 3 * plane * sizeof(double)));
     auto run = [&]() -> int {
         MRL_HIP(ctx, hipMemsetAsync(d_planar, 0, 3 * plane * sizeof(double), ctx->stream));
-        const size_t chunk = std::min(n, ctx->host_chunk);
-        const int rc = ensure_stage(ctx, chunk, 36);
-        if (rc != MRL_OK) return rc;
-        float *d_wi = (float *)ctx->d_stage, *d_wo = d_wi + 3 * chunk, *d_g = d_wo + 3 * chunk;
-        a.wi = d_wi; a.wo = d_wo; a.g = d_g; a.planar = d_planar;
-        for (size_t off = 0; off < n; off += chunk) {
-            const size_t m = std::min(chunk, n - off);
-            MRL_HIP(ctx, hipMemcpyAsync(d_wi, wi + 3 * off, 12 * m, hipMemcpyHostToDevice, ctx->stream));
-            MRL_HIP(ctx, hipMemcpyAsync(d_wo, wo + 3 * off, 12 * m, hipMemcpyHostToDevice, ctx->stream));
-            MRL_HIP(ctx, hipMemcpyAsync(d_g, grad_rgb + 3 * off, 12 * m, hipMemcpyHostToDevice, ctx->stream));
-            a.n = m;
+        a.planar = d_planar;
+        const int rc = run_host_staged(ctx, streams, n, 0, [&](char *const *addr, size_t m) -> int {
+            a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
             MRL_HIP(ctx, mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream));
-            MRL_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the stage is reused by the next chunk
-        }
+            return MRL_OK;
+        });
+        if (rc != MRL_OK) return rc;
         if (variant != 1) MRL_HIP(ctx, mrl::launch_table_grad_fold(a.bricks, d_planar, dims, a.param, ctx->compute_units, ctx->stream));
         std::vector<double> sums;
         try { sums.resize(3 * plane); } catch (const std::bad_alloc &) { return fail(ctx, MRL_ERR_OOM, "gradient buffer"); }

@@ -64,3 +64,17 @@ def test_image_file_header_planning_is_clean_under_asan_ubsan(tmp_path):
                            "-fno-omit-frame-pointer", "-o", exe, os.path.join(ROOT, "tests", "image_file_fuzz.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
     assert r.returncode == 0 and "image header fuzz ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ missing")
+def test_host_stage_layout_and_chunk_loop_are_clean_under_asan_ubsan(tmp_path):
+    """The host-array path of every whole-array call (csrc/merl_host_stage.hpp: stream list -> slot layout -> chunk loop, pure host C++):
+    the real layout function and the real loop against a memcpy mover and a stub kernel, one slot and two, slots of exactly the planned
+    size — outputs equal the straight computation, inputs untouched, streams inside the slot and disjoint, chunks that sum to n, the
+    byte cap, an error in the middle of a call."""
+    exe = str(tmp_path / "host_stage")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-o", exe, os.path.join(ROOT, "tests", "host_stage_asan.cpp"), "-lpthread"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "host stage ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
