@@ -158,10 +158,52 @@ class TileInputs(C.Structure):
     _fields_ = [("wi", C.c_void_p), ("wo", C.c_void_p), ("u", C.c_void_p), ("mat", C.c_void_p)]
 
 
+class PlanOp(C.Structure):
+    """mrl_plan_op: one operation of a sharded call's schedule (include/merl_hip.h)."""
+    _fields_ = [("kind", C.c_int), ("member", C.c_int), ("buffer", C.c_int), ("step", C.c_size_t), ("first", C.c_size_t),
+                ("count", C.c_size_t), ("tile_offset", C.c_size_t), ("after_transfer_of_step", C.c_longlong)]
+
+
+PLAN_COMPUTE, PLAN_TRANSFER = 0, 1
+
+
+class LinkReport(C.Structure):
+    """mrl_link_report: one peer -> root link of mrl_group_link_test."""
+    _fields_ = [("peer", C.c_int), ("ok", C.c_int), ("bytes", C.c_size_t), ("mismatches", C.c_size_t), ("ms", C.c_float), ("GBps", C.c_float)]
+
+
 class MerlHipError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
         super().__init__(f"{what}: status {status} ({detail})" if detail else f"{what}: status {status}")
         self.status = status
+
+
+# ---- the batch and queue calls, as csrc/merl_calls.hip describes them (for_each_stream): a call is a mode plus its ordered streams ----
+# A stream is (name, columns): None is [n], 0 is [n, width] with the family's width (3, n_channels or n_wavelengths).
+_WI, _WO, _U, _VALUES, _PDF = ("wi", 3), ("wo", 3), ("u", 2), ("out_values", 0), ("out_pdf", None)
+_MODES = {                  # mode: (inputs, outputs), both in ABI order
+    "eval":        ((_WI, _WO), (_VALUES,)),
+    "pdf":         ((_WI, _WO), (_PDF,)),
+    "eval_pdf":    ((_WI, _WO), (_VALUES, _PDF)),
+    "sample":      ((_WI, _U), (("out_wo", 3), _PDF, ("out_weight", 0))),
+    "eval_sample": ((_WI, _WO, _U), (_VALUES, _PDF, ("out_wo", 3), ("out_pdf2", None), ("out_weight", 0))),
+}
+_FAMILIES = {               # family: (symbol, the parameters between the inputs and the outputs by their names in include/merl_hip.h)
+    "batch":              ("mrl_{}_batch", ("mat", "single_id", "n")),
+    "queue":              ("mrl_{}_queue", ("mat", "single_id", "queue", "queue_count", "capacity")),
+    "batch_nch":          ("mrl_{}_batch_nch", ("mat", "single_id", "n", "n_channels")),
+    "queue_nch":          ("mrl_{}_queue_nch", ("mat", "single_id", "queue", "queue_count", "capacity", "n_channels")),
+    "spectral_batch":     ("mrl_{}_spectral_batch", ("wavelengths", "n_wavelengths", "id", "n")),
+    "spectral_queue":     ("mrl_{}_spectral_queue", ("wavelengths", "n_wavelengths", "mat", "single_id", "queue", "queue_count", "capacity")),
+    "spectral_batch_mat": ("mrl_{}_spectral_batch_mat", ("wavelengths", "n_wavelengths", "mat", "n")),
+    "group":              ("mrl_group_{}_batch", ("mat", "single_id", "n")),          # first argument: the group, not a context
+}
+_PDF_FAMILIES = ("batch", "queue", "group")         # the pdf is channel- and wavelength-free: the other families have no pdf mode
+_SCALARS = {"single_id": C.c_int32, "id": C.c_int32, "n": C.c_size_t, "capacity": C.c_size_t, "n_channels": C.c_int, "n_wavelengths": C.c_int}
+# (family, mode): (symbol, middle parameters, inputs, outputs)
+_CALLS = {(family, mode): (symbol.format(mode), middle) + streams
+          for family, (symbol, middle) in _FAMILIES.items() for mode, streams in _MODES.items()
+          if mode != "pdf" or family in _PDF_FAMILIES}
 
 
 _lib = None
@@ -193,6 +235,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_init.argtypes = [C.c_int, C.POINTER(vp)]
     L.mrl_destroy.argtypes = [vp]
     L.mrl_strerror.argtypes = [C.c_int]; L.mrl_strerror.restype = C.c_char_p
+    L.mrl_build_info.argtypes = []; L.mrl_build_info.restype = C.c_char_p
     L.mrl_last_error.argtypes = [vp]; L.mrl_last_error.restype = C.c_char_p
     L.mrl_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.mrl_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
@@ -209,18 +252,10 @@ def load_library(path: Optional[str] = None):
     L.mrl_material_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mrl_material_release.argtypes = [vp, C.c_int]
     L.mrl_memory_info.argtypes = [vp] + [C.POINTER(C.c_size_t)] * 4
-    L.mrl_eval_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp]
-    L.mrl_pdf_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp]
+    for symbol, middle, ins, outs in _CALLS.values():        # handle, inputs, middle parameters, outputs
+        getattr(L, symbol).argtypes = [vp] + [fp] * len(ins) + [_SCALARS.get(name, vp) for name in middle] + [fp] * len(outs)
     L.mrl_partition_by_material.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
-    L.mrl_eval_pdf_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
-    L.mrl_eval_pdf_queue.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
-    L.mrl_sample_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp, fp]
-    L.mrl_eval_sample_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp, fp, fp, fp]
-    L.mrl_eval_queue.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp]
-    L.mrl_pdf_queue.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp]
-    L.mrl_sample_queue.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp]
-    L.mrl_eval_sample_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp, fp, fp]
     L.mrl_generate_pairs.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, fp, fp, fp]
     L.mrl_generate_materials.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, vp]
     L.mrl_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -239,6 +274,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_scalar_eval_pdf.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mrl_scalar_sample.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mrl_material_param.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.mrl_material_sampling2d.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, C.c_size_t]
     L.mrl_material_host_table.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.mrl_host_table_retain.argtypes = [vp]
     L.mrl_host_table_release.argtypes = [vp]
@@ -246,14 +282,6 @@ def load_library(path: Optional[str] = None):
     L.mrl_host_eval_pdf.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mrl_host_sample.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mrl_host_eval_sample.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.mrl_eval_batch_nch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp]
-    L.mrl_sample_batch_nch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp, fp, fp]
-    L.mrl_eval_pdf_batch_nch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp, fp]
-    L.mrl_eval_sample_batch_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp, fp, fp, fp, fp]
-    L.mrl_eval_queue_nch.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp]
-    L.mrl_sample_queue_nch.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp, fp, fp]
-    L.mrl_eval_pdf_queue_nch.argtypes = [vp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp, fp]
-    L.mrl_eval_sample_queue_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp, fp, fp, fp, fp]
     L.mrl_tensor_file_open.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.mrl_tensor_file_close.argtypes = [vp]
     L.mrl_tensor_file_last_error.argtypes = [vp]; L.mrl_tensor_file_last_error.restype = C.c_char_p
@@ -266,18 +294,6 @@ def load_library(path: Optional[str] = None):
     L.mrl_material_upload_rgl.argtypes = [vp, C.POINTER(RglFields), C.POINTER(C.c_int)]
     L.mrl_material_upload_rgl_spectral.argtypes = [vp, C.POINTER(RglSpectralFields), C.POINTER(C.c_int)]
     L.mrl_material_wavelengths.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_size_t]
-    L.mrl_eval_spectral_batch.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp]
-    L.mrl_eval_pdf_spectral_batch.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp, fp]
-    L.mrl_sample_spectral_batch.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp, fp, fp]
-    L.mrl_eval_sample_spectral_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int, C.c_int32, C.c_size_t, fp, fp, fp, fp, fp]
-    L.mrl_eval_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp]
-    L.mrl_eval_pdf_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
-    L.mrl_sample_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp]
-    L.mrl_eval_sample_spectral_queue.argtypes = [vp, fp, fp, fp, fp, C.c_int, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp, fp, fp]
-    L.mrl_eval_spectral_batch_mat.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp]
-    L.mrl_eval_pdf_spectral_batch_mat.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp, fp]
-    L.mrl_sample_spectral_batch_mat.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp, fp, fp]
-    L.mrl_eval_sample_spectral_batch_mat.argtypes = [vp, fp, fp, fp, fp, C.c_int, vp, C.c_size_t, fp, fp, fp, fp, fp]
     cfp = C.POINTER(C.c_float)
     L.mrl_host_eval_pdf_spectral.argtypes = [vp, cfp, cfp, cfp, C.c_int, cfp, cfp]
     L.mrl_host_sample_spectral.argtypes = [vp, cfp, cfp, cfp, C.c_int, cfp, cfp, cfp]
@@ -297,6 +313,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_group_material_upload_table.argtypes = [vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.mrl_group_material_ggx.argtypes = [vp, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     L.mrl_group_material_upload_rgl.argtypes = [vp, C.POINTER(RglFields), C.POINTER(C.c_int)]
+    L.mrl_group_material_upload_rgl_spectral.argtypes = [vp, C.POINTER(RglSpectralFields), C.POINTER(C.c_int)]
     L.mrl_group_material_load_rgl.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
     L.mrl_group_material_release.argtypes = [vp, C.c_int]
     L.mrl_tile_bounds.argtypes = [C.c_size_t, C.c_int, C.c_int, szp, szp]; L.mrl_tile_bounds.restype = None
@@ -305,13 +322,10 @@ def load_library(path: Optional[str] = None):
     L.mrl_group_generate_tiles.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, C.POINTER(TileInputs)]
     L.mrl_group_eval_sample_sharded.argtypes = [vp, C.POINTER(TileInputs), C.c_int32, C.c_size_t, C.c_size_t, C.c_int, fp, fp, fp, fp, fp]
     L.mrl_group_eval_sharded.argtypes = [vp, C.POINTER(TileInputs), C.c_int32, C.c_size_t, C.c_size_t, C.c_int, fp]
-    L.mrl_group_eval_sample_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp, fp, fp, fp]
-    L.mrl_group_eval_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp]
-    L.mrl_group_pdf_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp]
-    L.mrl_group_eval_pdf_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
-    L.mrl_group_sample_batch.argtypes = [vp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp, fp]
     L.mrl_group_synchronize.argtypes = [vp]
     L.mrl_group_last_timing.argtypes = [vp, C.POINTER(C.c_float)]
+    L.mrl_group_plan.argtypes = [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(PlanOp), C.c_size_t]; L.mrl_group_plan.restype = C.c_size_t
+    L.mrl_group_link_test.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(LinkReport)]
     if path is None:
         _lib = L
     return L
@@ -341,6 +355,46 @@ def _addr(x, dtype, cols: Optional[int], n: Optional[int], name: str):
     if n is not None and shape != want_shape:
         raise ValueError(f"{name}: shape {shape}, expected {want_shape}")
     return ptr
+
+
+def _stream_call(owner, family, mode, ins, out=None, width=3, wavelengths=None, mat=None, material=0, queue=None, count=None, capacity=None):
+    """One batch or queue call of a MerlHip (family "group": of a MerlGroup) from its row of _CALLS.  ins: the mode's input arrays in ABI
+    order; n is wi's length.  Outputs the caller does not pass in `out` are allocated: like wi for whole arrays, zeros on wi's device for a
+    queue (unqueued slots are never written), numpy for a group.  Returns the output, or the outputs as a tuple in ABI order."""
+    symbol, middle, in_streams, out_streams = _CALLS[family, mode]
+    wi = ins[0]
+    n = int(wi.shape[0])
+    queued = "queue" in middle
+    if queued:
+        q, q_count, cap = owner._queue(wi, queue, count, capacity)
+    elif family != "group":
+        owner._prep(wi)
+    if wavelengths is not None:
+        width = wavelengths.shape[1]
+    elif width is None:
+        raise ValueError("wavelengths: need an [n, W] array (None, with n_wavelengths, means a single material's own nodes)")
+    width = int(width)
+    if out is None:
+        shapes = [(n,) if cols is None else (n, width if cols == 0 else cols) for _, cols in out_streams]
+        if family == "group":
+            out = tuple(np.empty(shape, np.float32) for shape in shapes)
+        else:
+            alloc = owner._zeros if queued else owner._empty
+            out = tuple(alloc(wi, shape) for shape in shapes)
+    else:
+        out = (out,) if len(out_streams) == 1 else tuple(out)
+        if len(out) != len(out_streams):
+            raise ValueError(f"out: {symbol} writes {len(out_streams)} arrays, got {len(out)}")
+    between = {"mat": _addr(mat, np.int32, None, n, "mat"), "single_id": material, "id": material, "n": n,
+               "n_channels": width, "n_wavelengths": width, "wavelengths": _addr(wavelengths, np.float32, width, n, "wavelengths")}
+    if queued:
+        between.update(queue=q, queue_count=q_count, capacity=cap)
+    args = [owner._g if family == "group" else owner._ctx]
+    args += [_addr(x, np.float32, cols, n, name) for (name, cols), x in zip(in_streams, ins)]
+    args += [between[name] for name in middle]
+    args += [_addr(x, np.float32, width if cols == 0 else cols, n, name) for (name, cols), x in zip(out_streams, out)]
+    owner._check(getattr(owner._lib, symbol)(*args), symbol)
+    return out[0] if len(out_streams) == 1 else out
 
 
 class MerlHip:
@@ -459,86 +513,32 @@ class MerlHip:
         self._check(self._lib.mrl_material_wavelengths(self._ctx, mid, C.byref(n), out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "mrl_material_wavelengths")
         return out
 
-    def eval_sample_spectral(self, wi, wo, u, wavelengths, material: int, n_wavelengths: Optional[int] = None):
+    def eval_sample_spectral(self, wi, wo, u, wavelengths, material: int, n_wavelengths: Optional[int] = None, out=None):
         """A spectral RGL material at per-unit wavelengths [n, W] (None: the file's own nodes, n_wavelengths = their number):
         (values [n, W], pdf, wo', pdf', weight' [n, W])."""
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1]) if wavelengths is not None else int(n_wavelengths)
-        out = (self._empty(wi, (n, W)), self._empty(wi, (n,)), self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, W)))
-        val, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_spectral_batch(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(wavelengths, np.float32, W, n, "wavelengths"), W, material, n,
-            _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"), _addr(wo2, np.float32, 3, n, "out_wo"),
-            _addr(pdf2, np.float32, None, n, "out_pdf2"), _addr(w, np.float32, W, n, "out_weight")), "mrl_eval_sample_spectral_batch")
-        return out
+        return _stream_call(self, "spectral_batch", "eval_sample", (wi, wo, u), out, n_wavelengths, wavelengths, material=material)
 
-    def eval_spectral(self, wi, wo, wavelengths, material: int, n_wavelengths: Optional[int] = None, with_pdf: bool = False):
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1]) if wavelengths is not None else int(n_wavelengths)
-        val = self._empty(wi, (n, W))
-        args = (self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W, material, n,
-                _addr(val, np.float32, W, n, "out_values"))
-        if with_pdf:
-            pdf = self._empty(wi, (n,))
-            self._check(self._lib.mrl_eval_pdf_spectral_batch(*args, _addr(pdf, np.float32, None, n, "out_pdf")), "mrl_eval_pdf_spectral_batch")
-            return val, pdf
-        self._check(self._lib.mrl_eval_spectral_batch(*args), "mrl_eval_spectral_batch")
-        return val
+    def eval_spectral(self, wi, wo, wavelengths, material: int, n_wavelengths: Optional[int] = None, with_pdf: bool = False, out=None):
+        return _stream_call(self, "spectral_batch", "eval_pdf" if with_pdf else "eval", (wi, wo), out, n_wavelengths, wavelengths, material=material)
 
-    def sample_spectral(self, wi, u, wavelengths, material: int, n_wavelengths: Optional[int] = None):
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1]) if wavelengths is not None else int(n_wavelengths)
-        wo2, pdf2, w = self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, W))
-        self._check(self._lib.mrl_sample_spectral_batch(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W, material, n,
-            _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf"), _addr(w, np.float32, W, n, "out_weight")), "mrl_sample_spectral_batch")
-        return wo2, pdf2, w
+    def sample_spectral(self, wi, u, wavelengths, material: int, n_wavelengths: Optional[int] = None, out=None):
+        return _stream_call(self, "spectral_batch", "sample", (wi, u), out, n_wavelengths, wavelengths, material=material)
 
     # ---- spectral materials with a material id per unit (whole arrays: host or device) ----
     # A unit whose id names no live spectral RGL material gets zeros; wavelengths [n, W] are required (materials may have different
     # node grids).  PARITY UNPINNED, as for the single-material calls.
-    def eval_sample_spectral_mat(self, wi, wo, u, wavelengths, mat):
+    def eval_sample_spectral_mat(self, wi, wo, u, wavelengths, mat, out=None):
         """(values [n, W], pdf, wo', pdf', weight' [n, W]) of the material mat[i] at wavelengths[i]."""
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1])
-        out = (self._empty(wi, (n, W)), self._empty(wi, (n,)), self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, W)))
-        val, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_spectral_batch_mat(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(wavelengths, np.float32, W, n, "wavelengths"), W, _addr(mat, np.int32, None, n, "mat"), n,
-            _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"), _addr(wo2, np.float32, 3, n, "out_wo"),
-            _addr(pdf2, np.float32, None, n, "out_pdf2"), _addr(w, np.float32, W, n, "out_weight")), "mrl_eval_sample_spectral_batch_mat")
-        return out
+        return _stream_call(self, "spectral_batch_mat", "eval_sample", (wi, wo, u), out, None, wavelengths, mat)
 
-    def eval_spectral_mat(self, wi, wo, wavelengths, mat):
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1])
-        val = self._empty(wi, (n, W))
-        self._check(self._lib.mrl_eval_spectral_batch_mat(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
-            _addr(mat, np.int32, None, n, "mat"), n, _addr(val, np.float32, W, n, "out_values")), "mrl_eval_spectral_batch_mat")
-        return val
+    def eval_spectral_mat(self, wi, wo, wavelengths, mat, out=None):
+        return _stream_call(self, "spectral_batch_mat", "eval", (wi, wo), out, None, wavelengths, mat)
 
-    def eval_pdf_spectral_mat(self, wi, wo, wavelengths, mat):
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1])
-        val, pdf = self._empty(wi, (n, W)), self._empty(wi, (n,))
-        self._check(self._lib.mrl_eval_pdf_spectral_batch_mat(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
-            _addr(mat, np.int32, None, n, "mat"), n, _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf")),
-            "mrl_eval_pdf_spectral_batch_mat")
-        return val, pdf
+    def eval_pdf_spectral_mat(self, wi, wo, wavelengths, mat, out=None):
+        return _stream_call(self, "spectral_batch_mat", "eval_pdf", (wi, wo), out, None, wavelengths, mat)
 
-    def sample_spectral_mat(self, wi, u, wavelengths, mat):
-        n = int(wi.shape[0]); self._prep(wi)
-        W = int(wavelengths.shape[1])
-        wo2, pdf2, w = self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, W))
-        self._check(self._lib.mrl_sample_spectral_batch_mat(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
-            _addr(mat, np.int32, None, n, "mat"), n, _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf"),
-            _addr(w, np.float32, W, n, "out_weight")), "mrl_sample_spectral_batch_mat")
-        return wo2, pdf2, w
+    def sample_spectral_mat(self, wi, u, wavelengths, mat, out=None):
+        return _stream_call(self, "spectral_batch_mat", "sample", (wi, u), out, None, wavelengths, mat)
 
     def load_rgl(self, path: str) -> int:
         """An RGL *.bsdf file (tensor_file container with the RGL field names; the *_rgb variant)."""
@@ -591,7 +591,6 @@ class MerlHip:
     def material_sampling2d(self, material: int = 0) -> np.ndarray:
         """The conditional sampling table P(theta_h | theta_i) as the device built it: [n_ti, 2 n_th + 1] doubles (cdf | c)."""
         n_ti, n_th = C.c_int(), C.c_int()
-        self._lib.mrl_material_sampling2d.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t]
         self._check(self._lib.mrl_material_sampling2d(self._ctx, int(material), C.byref(n_ti), C.byref(n_th), None, 0), "mrl_material_sampling2d")
         out = np.empty((n_ti.value, 2 * n_th.value + 1), np.float64)
         self._check(self._lib.mrl_material_sampling2d(self._ctx, int(material), None, None, out.ctypes.data, out.size), "mrl_material_sampling2d")
@@ -646,44 +645,17 @@ class MerlHip:
         return c.value
 
     def eval_nch(self, wi, wo, n_channels: int, mat=None, material: int = 0, out=None):
-        n = int(wi.shape[0]); self._prep(wi)
-        out = self._empty(wi, (n, n_channels)) if out is None else out
-        self._check(self._lib.mrl_eval_batch_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                 _addr(mat, np.int32, None, n, "mat"), material, n, n_channels,
-                                                 _addr(out, np.float32, n_channels, n, "out_values")), "mrl_eval_batch_nch")
-        return out
+        return _stream_call(self, "batch_nch", "eval", (wi, wo), out, n_channels, None, mat, material)
 
-    def sample_nch(self, wi, u, n_channels: int, mat=None, material: int = 0):
-        n = int(wi.shape[0]); self._prep(wi)
-        wo, pdf, w = self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, n_channels))
-        self._check(self._lib.mrl_sample_batch_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"),
-                                                   _addr(mat, np.int32, None, n, "mat"), material, n, n_channels,
-                                                   _addr(wo, np.float32, 3, n, "out_wo"), _addr(pdf, np.float32, None, n, "out_pdf"),
-                                                   _addr(w, np.float32, n_channels, n, "out_weight")), "mrl_sample_batch_nch")
-        return wo, pdf, w
+    def sample_nch(self, wi, u, n_channels: int, mat=None, material: int = 0, out=None):
+        return _stream_call(self, "batch_nch", "sample", (wi, u), out, n_channels, None, mat, material)
 
-    def eval_pdf_nch(self, wi, wo, n_channels: int, mat=None, material: int = 0):
-        n = int(wi.shape[0]); self._prep(wi)
-        val, pdf = self._empty(wi, (n, n_channels)), self._empty(wi, (n,))
-        self._check(self._lib.mrl_eval_pdf_batch_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                     _addr(mat, np.int32, None, n, "mat"), material, n, n_channels,
-                                                     _addr(val, np.float32, n_channels, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf")),
-                    "mrl_eval_pdf_batch_nch")
-        return val, pdf
+    def eval_pdf_nch(self, wi, wo, n_channels: int, mat=None, material: int = 0, out=None):
+        return _stream_call(self, "batch_nch", "eval_pdf", (wi, wo), out, n_channels, None, mat, material)
 
-    def eval_sample_nch(self, wi, wo, u, n_channels: int, mat=None, material: int = 0):
+    def eval_sample_nch(self, wi, wo, u, n_channels: int, mat=None, material: int = 0, out=None):
         """Returns (values[n, C], pdf, wo', pdf', weight'[n, C])."""
-        n = int(wi.shape[0]); self._prep(wi)
-        out = (self._empty(wi, (n, n_channels)), self._empty(wi, (n,)), self._empty(wi, (n, 3)), self._empty(wi, (n,)),
-               self._empty(wi, (n, n_channels)))
-        val, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_batch_nch(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(mat, np.int32, None, n, "mat"), material, n, n_channels,
-            _addr(val, np.float32, n_channels, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"),
-            _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf2"),
-            _addr(w, np.float32, n_channels, n, "out_weight")), "mrl_eval_sample_batch_nch")
-        return out
+        return _stream_call(self, "batch_nch", "eval_sample", (wi, wo, u), out, n_channels, None, mat, material)
 
     def load_tensor_table(self, path: str, field: Optional[str] = None):
         """A customized_measurement table stored in a tensor_file container.  Returns (material id, channels)."""
@@ -696,97 +668,36 @@ class MerlHip:
 
     def eval_sample_queue_nch(self, wi, wo, u, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None, out=None):
         """Fused n-channel unit over a wavefront queue; unqueued slots of `out` stay as they are."""
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        if out is None:
-            out = (self._zeros(wi, (n, n_channels)), self._zeros(wi, (n,)), self._zeros(wi, (n, 3)), self._zeros(wi, (n,)),
-                   self._zeros(wi, (n, n_channels)))
-        val, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_queue_nch(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, n_channels,
-            _addr(val, np.float32, n_channels, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"),
-            _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf2"),
-            _addr(w, np.float32, n_channels, n, "out_weight")), "mrl_eval_sample_queue_nch")
-        return out
+        return _stream_call(self, "queue_nch", "eval_sample", (wi, wo, u), out, n_channels, None, mat, material, queue, count, capacity)
 
     def eval_queue_nch(self, wi, wo, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None, out=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        out = self._zeros(wi, (n, n_channels)) if out is None else out
-        self._check(self._lib.mrl_eval_queue_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                 _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, n_channels,
-                                                 _addr(out, np.float32, n_channels, n, "out_values")), "mrl_eval_queue_nch")
-        return out
+        return _stream_call(self, "queue_nch", "eval", (wi, wo), out, n_channels, None, mat, material, queue, count, capacity)
 
-    def sample_queue_nch(self, wi, u, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        wo, pdf, w = self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, n_channels))
-        self._check(self._lib.mrl_sample_queue_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"),
-                                                   _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, n_channels,
-                                                   _addr(wo, np.float32, 3, n, "out_wo"), _addr(pdf, np.float32, None, n, "out_pdf"),
-                                                   _addr(w, np.float32, n_channels, n, "out_weight")), "mrl_sample_queue_nch")
-        return wo, pdf, w
+    def sample_queue_nch(self, wi, u, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None, out=None):
+        return _stream_call(self, "queue_nch", "sample", (wi, u), out, n_channels, None, mat, material, queue, count, capacity)
 
-    def eval_pdf_queue_nch(self, wi, wo, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        val, pdf = self._zeros(wi, (n, n_channels)), self._zeros(wi, (n,))
-        self._check(self._lib.mrl_eval_pdf_queue_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                     _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, n_channels,
-                                                     _addr(val, np.float32, n_channels, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf")),
-                    "mrl_eval_pdf_queue_nch")
-        return val, pdf
+    def eval_pdf_queue_nch(self, wi, wo, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None, out=None):
+        return _stream_call(self, "queue_nch", "eval_pdf", (wi, wo), out, n_channels, None, mat, material, queue, count, capacity)
 
     # ---- spectral materials over a wavefront queue (GPU tensors only) ----
     # wavelengths [n, W] per slot (None: the file's own nodes, n_wavelengths = their number; single material only); mat: a material id
     # per slot (None: `material`).  Unqueued slots of `out` stay as they are.  PARITY UNPINNED, as for the whole-array calls.
-    def _spectral_w(self, wavelengths, n_wavelengths):
-        return int(wavelengths.shape[1]) if wavelengths is not None else int(n_wavelengths)
-
     def eval_sample_spectral_queue(self, wi, wo, u, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
                                    n_wavelengths: Optional[int] = None):
         """Fused spectral unit over a wavefront queue: (values [n, W], pdf, wo', pdf', weight' [n, W])."""
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        W = self._spectral_w(wavelengths, n_wavelengths)
-        if out is None:
-            out = (self._zeros(wi, (n, W)), self._zeros(wi, (n,)), self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, W)))
-        val, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_spectral_queue(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(wavelengths, np.float32, W, n, "wavelengths"), W, _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
-            _addr(val, np.float32, W, n, "out_values"), _addr(pdf, np.float32, None, n, "out_pdf"), _addr(wo2, np.float32, 3, n, "out_wo"),
-            _addr(pdf2, np.float32, None, n, "out_pdf2"), _addr(w, np.float32, W, n, "out_weight")), "mrl_eval_sample_spectral_queue")
-        return out
+        return _stream_call(self, "spectral_queue", "eval_sample", (wi, wo, u), out, n_wavelengths, wavelengths, mat, material, queue, count, capacity)
 
     def eval_spectral_queue(self, wi, wo, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
                             n_wavelengths: Optional[int] = None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        W = self._spectral_w(wavelengths, n_wavelengths)
-        out = self._zeros(wi, (n, W)) if out is None else out
-        self._check(self._lib.mrl_eval_spectral_queue(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
-            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, _addr(out, np.float32, W, n, "out_values")), "mrl_eval_spectral_queue")
-        return out
+        return _stream_call(self, "spectral_queue", "eval", (wi, wo), out, n_wavelengths, wavelengths, mat, material, queue, count, capacity)
 
     def eval_pdf_spectral_queue(self, wi, wo, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
                                 n_wavelengths: Optional[int] = None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        W = self._spectral_w(wavelengths, n_wavelengths)
-        val, pdf = (self._zeros(wi, (n, W)), self._zeros(wi, (n,))) if out is None else out
-        self._check(self._lib.mrl_eval_pdf_spectral_queue(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
-            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, _addr(val, np.float32, W, n, "out_values"),
-            _addr(pdf, np.float32, None, n, "out_pdf")), "mrl_eval_pdf_spectral_queue")
-        return val, pdf
+        return _stream_call(self, "spectral_queue", "eval_pdf", (wi, wo), out, n_wavelengths, wavelengths, mat, material, queue, count, capacity)
 
     def sample_spectral_queue(self, wi, u, wavelengths, queue, count, mat=None, material: int = 0, capacity=None, out=None,
                               n_wavelengths: Optional[int] = None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        W = self._spectral_w(wavelengths, n_wavelengths)
-        wo2, pdf2, w = (self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, W))) if out is None else out
-        self._check(self._lib.mrl_sample_spectral_queue(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"), _addr(wavelengths, np.float32, W, n, "wavelengths"), W,
-            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap, _addr(wo2, np.float32, 3, n, "out_wo"),
-            _addr(pdf2, np.float32, None, n, "out_pdf"), _addr(w, np.float32, W, n, "out_weight")), "mrl_sample_spectral_queue")
-        return wo2, pdf2, w
+        return _stream_call(self, "spectral_queue", "sample", (wi, u), out, n_wavelengths, wavelengths, mat, material, queue, count, capacity)
 
     def release_material(self, mid: int):
         """Frees the material's device memory; its id becomes a tombstone (batch calls render it as zeros)."""
@@ -811,12 +722,7 @@ class MerlHip:
             self.use_torch_stream()
 
     def eval(self, wi, wo, mat=None, material: int = 0, out=None):
-        n = int(wi.shape[0]); self._prep(wi)
-        out = self._empty(wi, (n, 3)) if out is None else out
-        self._check(self._lib.mrl_eval_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                             _addr(mat, np.int32, None, n, "mat"), material, n,
-                                             _addr(out, np.float32, 3, n, "out_rgb")), "mrl_eval_batch")
-        return out
+        return _stream_call(self, "batch", "eval", (wi, wo), out, mat=mat, material=material)
 
     def table_grad(self, wi, wo, grad_rgb, material: int = 0, out=None):
         """G += A^T grad_rgb, the adjoint of eval in the planar table of an RGB table material (mrl_table_grad_batch) under the
@@ -843,45 +749,18 @@ class MerlHip:
         return out
 
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
-        n = int(wi.shape[0]); self._prep(wi)
-        out = self._empty(wi, (n,)) if out is None else out
-        self._check(self._lib.mrl_pdf_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                            _addr(mat, np.int32, None, n, "mat"), material, n,
-                                            _addr(out, np.float32, None, n, "out_pdf")), "mrl_pdf_batch")
-        return out
+        return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
 
     def eval_pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         """eval and pdf of the same pairs in one launch (Mitsuba 3's eval_pdf).  Returns (rgb, pdf)."""
-        n = int(wi.shape[0]); self._prep(wi)
-        rgb, pdf = out if out is not None else (self._empty(wi, (n, 3)), self._empty(wi, (n,)))
-        self._check(self._lib.mrl_eval_pdf_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                 _addr(mat, np.int32, None, n, "mat"), material, n,
-                                                 _addr(rgb, np.float32, 3, n, "out_rgb"), _addr(pdf, np.float32, None, n, "out_pdf")),
-                    "mrl_eval_pdf_batch")
-        return rgb, pdf
+        return _stream_call(self, "batch", "eval_pdf", (wi, wo), out, mat=mat, material=material)
 
     def sample(self, wi, u, mat=None, material: int = 0, out=None):
-        n = int(wi.shape[0]); self._prep(wi)
-        wo, pdf, w = out if out is not None else (self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, 3)))
-        self._check(self._lib.mrl_sample_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"),
-                                               _addr(mat, np.int32, None, n, "mat"), material, n,
-                                               _addr(wo, np.float32, 3, n, "out_wo"), _addr(pdf, np.float32, None, n, "out_pdf"),
-                                               _addr(w, np.float32, 3, n, "out_weight")), "mrl_sample_batch")
-        return wo, pdf, w
+        return _stream_call(self, "batch", "sample", (wi, u), out, mat=mat, material=material)
 
     def eval_sample(self, wi, wo, u, mat=None, material: int = 0, out=None):
         """The benchmarked unit.  Returns (rgb, pdf, wo', pdf', weight')."""
-        n = int(wi.shape[0]); self._prep(wi)
-        if out is None:
-            out = (self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, 3)), self._empty(wi, (n,)), self._empty(wi, (n, 3)))
-        rgb, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_batch(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(mat, np.int32, None, n, "mat"), material, n,
-            _addr(rgb, np.float32, 3, n, "out_rgb"), _addr(pdf, np.float32, None, n, "out_pdf"),
-            _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf2"),
-            _addr(w, np.float32, 3, n, "out_weight")), "mrl_eval_sample_batch")
-        return out
+        return _stream_call(self, "batch", "eval_sample", (wi, wo, u), out, mat=mat, material=material)
 
     # ---- wavefront queues (device tensors only) ----
     def _zeros(self, like, shape):
@@ -916,51 +795,19 @@ class MerlHip:
 
     def eval_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
         """eval() of the slots queue[0 .. min(count, capacity)); other slots of `out` stay as they are."""
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        out = self._zeros(wi, (n, 3)) if out is None else out
-        self._check(self._lib.mrl_eval_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                             _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
-                                             _addr(out, np.float32, 3, n, "out_rgb")), "mrl_eval_queue")
-        return out
+        return _stream_call(self, "queue", "eval", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
 
     def pdf_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        out = self._zeros(wi, (n,)) if out is None else out
-        self._check(self._lib.mrl_pdf_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
-                                            _addr(out, np.float32, None, n, "out_pdf")), "mrl_pdf_queue")
-        return out
+        return _stream_call(self, "queue", "pdf", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
 
     def eval_pdf_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        rgb, pdf = out if out is not None else (self._zeros(wi, (n, 3)), self._zeros(wi, (n,)))
-        self._check(self._lib.mrl_eval_pdf_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                 _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
-                                                 _addr(rgb, np.float32, 3, n, "out_rgb"), _addr(pdf, np.float32, None, n, "out_pdf")),
-                    "mrl_eval_pdf_queue")
-        return rgb, pdf
+        return _stream_call(self, "queue", "eval_pdf", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
 
     def sample_queue(self, wi, u, queue, count, mat=None, material: int = 0, capacity=None, out=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        wo, pdf, w = out if out is not None else (self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, 3)))
-        self._check(self._lib.mrl_sample_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"),
-                                               _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
-                                               _addr(wo, np.float32, 3, n, "out_wo"), _addr(pdf, np.float32, None, n, "out_pdf"),
-                                               _addr(w, np.float32, 3, n, "out_weight")), "mrl_sample_queue")
-        return wo, pdf, w
+        return _stream_call(self, "queue", "sample", (wi, u), out, 3, None, mat, material, queue, count, capacity)
 
     def eval_sample_queue(self, wi, wo, u, queue, count, mat=None, material: int = 0, capacity=None, out=None):
-        n = int(wi.shape[0]); q, c, cap = self._queue(wi, queue, count, capacity)
-        if out is None:
-            out = (self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, 3)), self._zeros(wi, (n,)), self._zeros(wi, (n, 3)))
-        rgb, pdf, wo2, pdf2, w = out
-        self._check(self._lib.mrl_eval_sample_queue(
-            self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(mat, np.int32, None, n, "mat"), material, q, c, cap,
-            _addr(rgb, np.float32, 3, n, "out_rgb"), _addr(pdf, np.float32, None, n, "out_pdf"),
-            _addr(wo2, np.float32, 3, n, "out_wo"), _addr(pdf2, np.float32, None, n, "out_pdf2"),
-            _addr(w, np.float32, 3, n, "out_weight")), "mrl_eval_sample_queue")
-        return out
+        return _stream_call(self, "queue", "eval_sample", (wi, wo, u), out, 3, None, mat, material, queue, count, capacity)
 
     # ---- synthetic inputs (device) ----
     def generate_pairs(self, seed: int, first: int, n: int, out=None):
@@ -1022,7 +869,6 @@ def read_tensor_file(path: str) -> dict:
 def build_info() -> str:
     """mrl_build_info: "sources <hash>" of the loaded library."""
     L = load_library()
-    L.mrl_build_info.restype = C.c_char_p
     return L.mrl_build_info().decode()
 
 
@@ -1043,30 +889,14 @@ def chunk_steps(n_total: int, world: int, chunk: int) -> int:
     return int(load_library().mrl_chunk_steps(n_total, world, chunk))
 
 
-class PlanOp(C.Structure):
-    """mrl_plan_op: one operation of a sharded call's schedule (include/merl_hip.h)."""
-    _fields_ = [("kind", C.c_int), ("member", C.c_int), ("buffer", C.c_int), ("step", C.c_size_t), ("first", C.c_size_t),
-                ("count", C.c_size_t), ("tile_offset", C.c_size_t), ("after_transfer_of_step", C.c_longlong)]
-
-
-PLAN_COMPUTE, PLAN_TRANSFER = 0, 1
-
-
 def group_plan(n_total: int, world: int, chunk: int, root: int):
     """mrl_group_plan: the operations of one sharded call in issue order (pure arithmetic: needs no GPU)."""
     L = load_library()
-    L.mrl_group_plan.restype = C.c_size_t
-    L.mrl_group_plan.argtypes = [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(PlanOp), C.c_size_t]
     n = L.mrl_group_plan(n_total, world, chunk, root, None, 0)
     ops = (PlanOp * max(n, 1))()
     got = L.mrl_group_plan(n_total, world, chunk, root, ops, n)
     assert got == n
     return [ops[i] for i in range(n)]
-
-
-class LinkReport(C.Structure):
-    """mrl_link_report: one peer -> root link of mrl_group_link_test."""
-    _fields_ = [("peer", C.c_int), ("ok", C.c_int), ("bytes", C.c_size_t), ("mismatches", C.c_size_t), ("ms", C.c_float), ("GBps", C.c_float)]
 
 
 class MerlGroup:
@@ -1076,7 +906,6 @@ class MerlGroup:
         """mrl_group_link_test: one payload from every peer to the root, timed and bit-checked; list of dicts."""
         n = int(self._lib.mrl_group_size(self._g))
         rep = (LinkReport * n)()
-        self._lib.mrl_group_link_test.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(LinkReport)]
         rc = self._lib.mrl_group_link_test(self._g, nbytes, transport, root, rep)
         if rc != 0:
             raise MerlHipError(rc, "mrl_group_link_test", (self._lib.mrl_group_last_error(self._g) or b"").decode())
@@ -1167,46 +996,21 @@ class MerlGroup:
                                                      _addr(out_rgb, np.float32, 3, n_total, "out_rgb")), "mrl_group_eval_sharded")
         return out_rgb
 
-    def eval_sample_host(self, wi, wo, u, mat=None, material: int = 0):
+    def eval_sample_host(self, wi, wo, u, mat=None, material: int = 0, out=None):
         """Host (numpy) arrays split over the members, staged concurrently; returns numpy outputs."""
-        n = int(wi.shape[0])
-        out = (np.empty((n, 3), np.float32), np.empty((n,), np.float32), np.empty((n, 3), np.float32),
-               np.empty((n,), np.float32), np.empty((n, 3), np.float32))
-        self._check(self._lib.mrl_group_eval_sample_batch(
-            self._g, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"), _addr(u, np.float32, 2, n, "u"),
-            _addr(mat, np.int32, None, n, "mat"), material, n,
-            *[_addr(o, np.float32, c, n, "out") for o, c in zip(out, (3, None, 3, None, 3))]), "mrl_group_eval_sample_batch")
-        return out
+        return _stream_call(self, "group", "eval_sample", (wi, wo, u), out, mat=mat, material=material)
 
-    def eval_host(self, wi, wo, mat=None, material: int = 0):
-        n = int(wi.shape[0]); out = np.empty((n, 3), np.float32)
-        self._check(self._lib.mrl_group_eval_batch(self._g, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                   _addr(mat, np.int32, None, n, "mat"), material, n, _addr(out, np.float32, 3, n, "out_rgb")),
-                    "mrl_group_eval_batch")
-        return out
+    def eval_host(self, wi, wo, mat=None, material: int = 0, out=None):
+        return _stream_call(self, "group", "eval", (wi, wo), out, mat=mat, material=material)
 
-    def pdf_host(self, wi, wo, mat=None, material: int = 0):
-        n = int(wi.shape[0]); out = np.empty((n,), np.float32)
-        self._check(self._lib.mrl_group_pdf_batch(self._g, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                  _addr(mat, np.int32, None, n, "mat"), material, n, _addr(out, np.float32, None, n, "out_pdf")),
-                    "mrl_group_pdf_batch")
-        return out
+    def pdf_host(self, wi, wo, mat=None, material: int = 0, out=None):
+        return _stream_call(self, "group", "pdf", (wi, wo), out, mat=mat, material=material)
 
-    def eval_pdf_host(self, wi, wo, mat=None, material: int = 0):
-        n = int(wi.shape[0]); rgb, pdf = np.empty((n, 3), np.float32), np.empty((n,), np.float32)
-        self._check(self._lib.mrl_group_eval_pdf_batch(self._g, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                       _addr(mat, np.int32, None, n, "mat"), material, n,
-                                                       _addr(rgb, np.float32, 3, n, "out_rgb"), _addr(pdf, np.float32, None, n, "out_pdf")),
-                    "mrl_group_eval_pdf_batch")
-        return rgb, pdf
+    def eval_pdf_host(self, wi, wo, mat=None, material: int = 0, out=None):
+        return _stream_call(self, "group", "eval_pdf", (wi, wo), out, mat=mat, material=material)
 
-    def sample_host(self, wi, u, mat=None, material: int = 0):
-        n = int(wi.shape[0]); wo, pdf, w = np.empty((n, 3), np.float32), np.empty((n,), np.float32), np.empty((n, 3), np.float32)
-        self._check(self._lib.mrl_group_sample_batch(self._g, _addr(wi, np.float32, 3, n, "wi"), _addr(u, np.float32, 2, n, "u"),
-                                                     _addr(mat, np.int32, None, n, "mat"), material, n,
-                                                     _addr(wo, np.float32, 3, n, "out_wo"), _addr(pdf, np.float32, None, n, "out_pdf"),
-                                                     _addr(w, np.float32, 3, n, "out_weight")), "mrl_group_sample_batch")
-        return wo, pdf, w
+    def sample_host(self, wi, u, mat=None, material: int = 0, out=None):
+        return _stream_call(self, "group", "sample", (wi, u), out, mat=mat, material=material)
 
     def synchronize(self):
         self._check(self._lib.mrl_group_synchronize(self._g), "mrl_group_synchronize")
