@@ -589,9 +589,10 @@ MRL_HD float cos_or_nan32(float wi_sum, float wox, float woy, float woz, bool no
     const float t = wi_sum + (wox + woy + woz);                     // NaN or inf iff some component is
     return (__builtin_fabsf(t) <= 3.0e38f) ? (no_cosine ? 1.0f : woz) : __builtin_nanf("");
 }
-MRL_HD double cos_or_nan(float wix, float wiy, float wiz, float wox, float woy, float woz)
+// GGX (the cosine of wo is part of the model): 1.0, or NaN when a component of wi or wo — wo.z = inf included — is not finite
+MRL_HD double one_or_nan(float wix, float wiy, float wiz, float wox, float woy, float woz)
 {
-    return (double)cos_or_nan32((wix + wiy + wiz), wox, woy, woz);
+    return (double)cos_or_nan32((wix + wiy + wiz), wox, woy, woz, true);
 }
 
 // a5 tail: rgb = f cos(theta_o) in Float (the plugin's own arithmetic: Spectrum * Float); zero for a pair that fails the

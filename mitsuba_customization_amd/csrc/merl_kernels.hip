@@ -333,7 +333,7 @@ __device__ __forceinline__ void ggx_lane(const MaterialDev &m, UnitIO &io, const
         double v[3], p;
         fast::ggx_eval_pdf(g, in, out, v, p);
         const bool valid = (io.wiz > 0.0f) && (io.woz > 0.0f);
-        const double poison = fast::cos_or_nan(io.wix, io.wiy, io.wiz, io.wox, io.woy, 1.0f);
+        const double poison = fast::one_or_nan(io.wix, io.wiy, io.wiz, io.wox, io.woy, io.woz);
         io.rgb[0] = valid ? (float)(v[0] * poison) : 0.0f; io.rgb[1] = valid ? (float)(v[1] * poison) : 0.0f;
         io.rgb[2] = valid ? (float)(v[2] * poison) : 0.0f;
         if constexpr (mode_pdf(MODE)) io.pdf = valid ? (float)(p * poison) : 0.0f;
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(kBlock) void k_ggx(BatchArgs a)
             double v[3], p;
             fast::ggx_eval_pdf(g, in, out, v, p);
             const bool valid = (wiz > 0.0f) && (woz > 0.0f);
-            const double poison = fast::cos_or_nan(wix, wiy, wiz, wox, woy, 1.0f);     // 1.0, or NaN for non-finite input
+            const double poison = fast::one_or_nan(wix, wiy, wiz, wox, woy, woz);     // 1.0, or NaN for non-finite input
             if constexpr (HAS_EVAL) {
                 const float rgb[3] = { valid ? (float)(v[0] * poison) : 0.0f, valid ? (float)(v[1] * poison) : 0.0f,
                                        valid ? (float)(v[2] * poison) : 0.0f };

@@ -74,7 +74,7 @@ __device__ __forceinline__ void ggx_unit(const MaterialDev &m, int want, float w
         double v[3], p;
         fast::ggx_eval_pdf(g, in, o, v, p);
         const bool valid = (wiz > 0.0f) && (woz > 0.0f);
-        const double poison = fast::cos_or_nan(wix, wiy, wiz, wox, woy, 1.0f);
+        const double poison = fast::one_or_nan(wix, wiy, wiz, wox, woy, woz);
         out[0] = valid ? (float)(v[0] * poison) : 0.0f; out[1] = valid ? (float)(v[1] * poison) : 0.0f; out[2] = valid ? (float)(v[2] * poison) : 0.0f;
         out[3] = valid ? (float)(p * poison) : 0.0f;
     }
