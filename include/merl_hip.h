@@ -474,6 +474,22 @@ int mrl_eval_sample_queue(mrl_ctx *ctx, const float *wi, const float *wo, const 
                           const uint32_t *queue, const uint32_t *queue_count, size_t capacity,
                           float *out_rgb, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight);
 
+/* Which kernels an RGB call (mrl_*_batch, mrl_*_queue) launches, as data — pure arithmetic, no context and no device; the library's
+ * own launcher walks the same function.  mode: 0 eval, 1 pdf, 2 sample, 3 eval + sample, 4 eval + pdf; variant, layout, lookup,
+ * negative: the values of MRL_OPT_KERNEL, MRL_OPT_TABLE_LAYOUT, MRL_OPT_LOOKUP, MRL_OPT_NEGATIVE; any_standard: some table the call may meet is
+ * in a standard parameterisation; queued: a mrl_*_queue call; has_ggx / has_table: the context holds analytic / table materials; n:
+ * units (a queue's capacity).  out[i].kernel is the kernel's name as the code object spells it (demangled, without namespace and
+ * arguments); its grid is min(ceil(n / block), compute units * blocks_per_cu) blocks, at least one, rounded up to a multiple of 8
+ * where whole_xcds is set (blocks_per_cu 0: one block; the two segment kernels of a kind partition take at most that many
+ * blocks).  Returns the number of launches (also when out is NULL or max_out too small); 0 for a value that names no mode. */
+enum mrl_route_material { MRL_ROUTE_ONE_TABLE = 0, MRL_ROUTE_ONE_GGX = 1, MRL_ROUTE_IDS = 2 };
+typedef struct mrl_route_launch {
+    char kernel[64];
+    int block, blocks_per_cu, whole_xcds;
+} mrl_route_launch;
+size_t mrl_batch_route(int mode, int variant, int layout, int lookup, int negative, int any_standard, int material, int queued,
+                       int has_ggx, int has_table, size_t n, mrl_route_launch *out, size_t max_out);
+
 /* ---- fitting tables: the adjoint of eval ----
  * With MRL_OPT_NEGATIVE at clamp or keep, eval of an RGB table material is linear in the uploaded planar array T: eval(T) = A T,
  * where row u of A holds, for unit u and channel c, guard x (cos(theta_o), or 1 with MRL_OPT_COSINE_FACTOR = 1) x scale[c] x the

@@ -103,44 +103,42 @@ int check_call(mrl_ctx *ctx, const BatchCall &c, const StreamList &streams)
     return MRL_OK;
 }
 
-int launch_device(mrl_ctx *ctx, const BatchCall &c)
+// The launches of one call on device pointers, in order; queue != nullptr: over a caller's queue of unit indices (c.n = its capacity)
+int launch_device(mrl_ctx *ctx, const BatchCall &c, const uint32_t *queue = nullptr, const uint32_t *queue_count = nullptr)
 {
-    const DeviceCall d = device_call(ctx, c);
-    const mrl::BatchArgs &a = d.args;
+    DeviceCall d = device_call(ctx, c);
+    mrl::BatchArgs &a = d.args;
+    a.idx = queue; a.idx_count = queue_count;
+    const int cus = ctx->compute_units;
     if (!d.multi && (a.single.kind == mrl::KIND_RGL || a.single.kind == mrl::KIND_RGL_SPECTRAL)) {     // adaptive-parameterisation material: its own kernel (spectral: pdf only)
-        MRL_HIP(ctx, mrl::launch_rgl(c.mode, a, &ctx->materials[(size_t)c.single_id].rgl, false, ctx->rgl_search, ctx->compute_units, ctx->stream));
+        MRL_HIP(ctx, mrl::launch_rgl(c.mode, a, &ctx->materials[(size_t)c.single_id].rgl, ctx->rgl_search, cus, ctx->stream));
         return MRL_OK;
     }
     if (c.n_ch > 0 && c.mode != mrl::MODE_PDF) {                          // n-channel tables: their own kernels (pdf is channel-free)
-        MRL_HIP(ctx, mrl::launch_batch_nch(c.mode, a, d.multi, c.n_ch, ctx->compute_units, ctx->stream));
+        MRL_HIP(ctx, mrl::launch_batch_nch(c.mode, a, c.n_ch, cus, ctx->stream));
         return MRL_OK;
     }
-    const bool multi = d.multi, has_ggx = d.has_ggx, has_table = d.has_table;
-    // MRL_OPT_KERNEL >= 4: a batch that may mix table and analytic materials is split into one dense queue
-    // per kind (count / scan / partition, no atomics); each queue then runs through its dedicated kernel
-    if (multi && has_ggx && has_table && ctx->kernel_variant >= 4 && c.mode != mrl::MODE_PDF && ctx->table_layout == mrl::LAYOUT_BRICK &&
-        ctx->opts.lookup == 1 && c.n < ((size_t)1 << 32)) {
+    const mrl::BatchRoute route = { ctx->kernel_variant, ctx->table_layout, d.has_ggx, d.has_table, true };
+    if (mrl::route_partitions(c.mode, a, route)) {             // count / scan / partition (no atomics), then each kind's dense queue
         uint32_t segments = 0, seg_len = 0;
-        mrl::partition_geometry(c.n, ctx->compute_units, &segments, &seg_len);
+        mrl::partition_geometry(c.n, cus, &segments, &seg_len);
         if (segments > kMaxSegments) return fail(ctx, MRL_ERR_INVALID, "partition geometry");
         DeviceBuf &queues = ctx->buf[mrl_ctx::BUF_QUEUES];
         int rc = queues.reserve(ctx, (2 * c.n + 4 * kMaxSegments + 2) * sizeof(uint32_t));
         if (rc != MRL_OK) return rc;
         uint32_t *q_table = (uint32_t *)queues.p, *q_ggx = q_table + c.n, *work = q_ggx + c.n;
-        MRL_HIP(ctx, mrl::launch_partition_kinds(c.mat, c.n, ctx->d_materials, a.n_materials, q_table, q_ggx, work,
-                                                 segments, seg_len, ctx->stream));
+        MRL_HIP(ctx, mrl::launch_partition_kinds(c.mat, c.n, ctx->d_materials, a.n_materials, q_table, q_ggx, work, segments, seg_len, ctx->stream));
         const uint32_t *totals = work + 4 * (size_t)segments;
         mrl::BatchArgs qa = a;
         qa.idx = q_table; qa.idx_count = totals;
-        MRL_HIP(ctx, mrl::launch_batch_queue(c.mode, qa, false, ctx->compute_units, ctx->stream));
+        MRL_HIP(ctx, mrl::launch_batch(c.mode, qa, mrl::kind_queue_route(route, false), cus, ctx->stream));
         qa.idx = q_ggx; qa.idx_count = totals + 1;
-        MRL_HIP(ctx, mrl::launch_batch_queue(c.mode, qa, true, ctx->compute_units, ctx->stream));
-        if (d.has_rgl) MRL_HIP(ctx, mrl::launch_rgl(c.mode, a, nullptr, false, ctx->rgl_search, ctx->compute_units, ctx->stream));
-        return MRL_OK;
+        MRL_HIP(ctx, mrl::launch_batch(c.mode, qa, mrl::kind_queue_route(route, true), cus, ctx->stream));
+    } else {
+        MRL_HIP(ctx, mrl::launch_batch(c.mode, a, route, cus, ctx->stream));
     }
-    MRL_HIP(ctx, mrl::launch_batch(c.mode, a, multi, ctx->kernel_variant, ctx->table_layout, has_ggx, has_table, ctx->compute_units, ctx->stream));
     // the context holds RGL materials: their units (zeros so far) are evaluated by a second launch on the same stream
-    if (multi && d.has_rgl) MRL_HIP(ctx, mrl::launch_rgl(c.mode, a, nullptr, false, ctx->rgl_search, ctx->compute_units, ctx->stream));
+    if (d.multi && d.has_rgl) MRL_HIP(ctx, mrl::launch_rgl(c.mode, a, nullptr, ctx->rgl_search, cus, ctx->stream));
     return MRL_OK;
 }
 
@@ -259,19 +257,7 @@ int run_queue(mrl_ctx *ctx, const BatchCall &c, const uint32_t *queue, const uin
     if (c.n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
     MRL_HIP(ctx, hipSetDevice(ctx->device));
     if (common_kind({ queue, queue_count }, streams) != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
-    DeviceCall d = device_call(ctx, c);
-    d.args.idx = queue; d.args.idx_count = queue_count;
-    if (!d.multi && (d.args.single.kind == mrl::KIND_RGL || d.args.single.kind == mrl::KIND_RGL_SPECTRAL)) {   // (spectral: pdf only, see check_call)
-        MRL_HIP(ctx, mrl::launch_rgl(c.mode, d.args, &ctx->materials[(size_t)c.single_id].rgl, true, ctx->rgl_search, ctx->compute_units, ctx->stream));
-        return MRL_OK;
-    }
-    if (c.n_ch > 0 && c.mode != mrl::MODE_PDF) {                          // n-channel tables: the same kernels walk the queue
-        MRL_HIP(ctx, mrl::launch_batch_nch(c.mode, d.args, d.multi, c.n_ch, ctx->compute_units, ctx->stream));
-        return MRL_OK;
-    }
-    MRL_HIP(ctx, mrl::launch_batch_indexed(c.mode, d.args, d.multi, ctx->table_layout, d.has_ggx, d.has_table, ctx->compute_units, ctx->stream));
-    if (d.multi && d.has_rgl) MRL_HIP(ctx, mrl::launch_rgl(c.mode, d.args, nullptr, true, ctx->rgl_search, ctx->compute_units, ctx->stream));
-    return MRL_OK;
+    return launch_device(ctx, c, queue, queue_count);
 }
 
 } // namespace mrlabi
@@ -364,6 +350,43 @@ int mrl_eval_sample_queue(mrl_ctx *ctx, const float *wi, const float *wo, const 
                           float *out_rgb, float *out_pdf, float *out_wo, float *out_pdf2, float *out_weight)
 {
     return run_queue(ctx, { mrl::MODE_EVAL_SAMPLE, wi, wo, u, mat, single_id, capacity, out_rgb, out_pdf, out_wo, out_pdf2, out_weight }, queue, queue_count);
+}
+
+size_t mrl_batch_route(int mode, int variant, int layout, int lookup, int negative, int any_standard, int material, int queued,
+                       int has_ggx, int has_table, size_t n, mrl_route_launch *out, size_t max_out)
+{
+    if (mode < mrl::MODE_EVAL || mode > mrl::MODE_EVAL_PDF) return 0;
+    static const int32_t ids = 0;
+    static const uint32_t queue = 0;
+    mrl::BatchArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n = n; a.any_standard = any_standard; a.opts.lookup = lookup; a.opts.negative = negative;
+    a.single.kind = material == MRL_ROUTE_ONE_GGX ? mrl::KIND_GGX : mrl::KIND_MERL;
+    if (material == MRL_ROUTE_IDS) a.mat = &ids;                // (the route reads which pointers are set, never what they point to)
+    if (queued) a.idx = a.idx_count = &queue;
+    const mrl::BatchRoute route = { variant, layout, has_ggx != 0, has_table != 0, true };
+    size_t count = 0;
+    auto emit = [&](const std::string &kernel, int block, int blocks_per_cu, bool whole_xcds) {
+        if (out && count < max_out) {
+            mrl_route_launch &l = out[count];
+            std::snprintf(l.kernel, sizeof l.kernel, "%s", kernel.c_str());
+            l.block = block; l.blocks_per_cu = blocks_per_cu; l.whole_xcds = whole_xcds;
+        }
+        ++count;
+    };
+    auto emit_route = [&](const mrl::BatchRoute &r) {
+        const mrl::KernelChoice k = mrl::route_batch(mode, a, r);
+        emit(mrl::kernel_name(k), k.block, k.blocks_per_cu, k.whole_xcds);
+    };
+    if (mrl::route_partitions(mode, a, route)) {                // launch_partition_kinds, then launch_device's two queue launches
+        emit("k_count_kinds", 256, 8, false); emit("k_scan_segments", 256, 0, false); emit("k_partition_kinds", 256, 8, false);
+        a.idx = a.idx_count = &queue;
+        emit_route(mrl::kind_queue_route(route, false));
+        emit_route(mrl::kind_queue_route(route, true));
+    } else {
+        emit_route(route);
+    }
+    return count;
 }
 
 int mrl_generate_pairs(mrl_ctx *ctx, uint64_t seed, uint64_t first_index, size_t n, float *wi, float *wo, float *u)

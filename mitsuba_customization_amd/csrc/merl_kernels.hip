@@ -2,13 +2,16 @@
 //
 // One lane = one unit (pair) per step.  Streams (wi, wo, u in; rgb, pdf, wo', pdf', weight out) are
 // contiguous per wave: 768 B (xyz) / 512 B (uv) / 256 B (scalar) per wave-instruction.
-//   k_batch        generic: every material kind, ocml f64 math (MRL_OPT_KERNEL 0, the A/B baseline)
-//   k_table        tuned f64 math, one lane gathers its own texels (variants 1/2; nearest lookups, rows layout)
-//   k_table_dma    brick layout + cooperative LDS-DMA fetch of the neighbourhood (variant 3, the default)
+//   k_batch        generic: every material kind, ocml f64 math
+//   k_table        tuned f64 math, one lane gathers its own texels
+//   k_table_dma    brick layout + cooperative LDS-DMA fetch of the neighbourhood
 //   k_ggx          tuned analytic GGX rough conductor
-//   k_count_kinds / k_scan_segments / k_partition_kinds   ballot/prefix partition of kind-mixed batches (variant 4)
+//   (which call takes which of these four: route_batch, merl_kernels.hpp)
+//   k_count_kinds / k_scan_segments / k_partition_kinds   ballot/prefix partition of kind-mixed batches
 //   k_build_bricks / k_build_rows   table re-layout at upload;  k_generate_*   synthetic inputs
 // What bounds each of them, with counter evidence: DESIGN.md §5-6.
+#include <cstdio>
+
 #include "merl_kernels.hpp"
 #include "merl_table_fast.hpp"
 #include "merl_ggx_fast.hpp"
@@ -884,85 +887,83 @@ __global__ __launch_bounds__(kBlock) void k_generate_materials(uint64_t seed, ui
 
 // 8 x 256-thread blocks per CU, grid-stride the rest
 inline unsigned grid_for(size_t n, int compute_units) { return grid_blocks(n, kBlock, (size_t)compute_units * 8); }
-// the LDS-DMA kernel: as many blocks as its LDS lets one CU hold (2 for the fused mode, 4 otherwise)
-template <int MODE>
-unsigned dma_grid(size_t n, int compute_units, bool whole_xcds)
-{
-    return grid_blocks(n, kDmaBlock, (size_t)compute_units * dma_blocks_per_cu(MODE), whole_xcds);
-}
 
-// runtime (multi, nt, lookup, layout) -> compile-time kernel
-template <int MODE, bool MULTI, bool NT, int LOOKUP>
-void launch_table3(const BatchArgs &a, int layout, dim3 grid, dim3 block, hipStream_t stream)
+// runtime flags -> f(std::bool_constant<flag>{}...), the way with_mode turns a mode into a template argument
+template <class F> auto with_flags(F &&f) { return f(); }
+template <class F, class... Rest>
+auto with_flags(F &&f, bool flag, Rest... rest)
 {
-    if (layout == LAYOUT_BRICK) hipLaunchKernelGGL((k_table<MODE, MULTI, NT, LOOKUP, LAYOUT_BRICK>), grid, block, 0, stream, a);
-    else                        hipLaunchKernelGGL((k_table<MODE, MULTI, NT, LOOKUP, LAYOUT_ROWS>), grid, block, 0, stream, a);
-}
-template <int MODE, bool MULTI, bool NT>
-void launch_table2(const BatchArgs &a, int lookup, int layout, dim3 grid, dim3 block, hipStream_t stream)
-{
-    if (lookup) launch_table3<MODE, MULTI, NT, 1>(a, layout, grid, block, stream);
-    else        launch_table3<MODE, MULTI, NT, 0>(a, layout, grid, block, stream);
-}
-// the LDS-DMA kernel in its half/diff-only or its every-parameterisation build (BatchArgs::any_standard); MODE, g, b, stream, a in scope
-#define MRL_DMA_LAUNCH(MULTI_, GGX_, INDEXED_)                                                                         \
-    do {                                                                                                               \
-        if (a.any_standard || a.opts.negative == NEGATIVE_RENORMALISE)                                                 \
-            hipLaunchKernelGGL((k_table_dma<MODE, MULTI_, true, GGX_, INDEXED_, true>), g, b, 0, stream, a);           \
-        else                hipLaunchKernelGGL((k_table_dma<MODE, MULTI_, true, GGX_, INDEXED_, false>), g, b, 0, stream, a); \
-    } while (0)
-
-template <int MODE>
-void launch_table(const BatchArgs &a, bool multi, bool nt, int lookup, int layout, dim3 grid, dim3 block, hipStream_t stream)
-{
-    if (multi) { if (nt) launch_table2<MODE, true, true>(a, lookup, layout, grid, block, stream); else launch_table2<MODE, true, false>(a, lookup, layout, grid, block, stream); }
-    else       { if (nt) launch_table2<MODE, false, true>(a, lookup, layout, grid, block, stream); else launch_table2<MODE, false, false>(a, lookup, layout, grid, block, stream); }
+    auto bind = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return flag ? bind(std::true_type{}) : bind(std::false_type{});
 }
 
 template <int MODE>
-hipError_t launch_mode(const BatchArgs &a, bool multi, int variant, int layout, bool has_ggx, bool has_table, int compute_units, hipStream_t stream)
+hipError_t launch_choice(const KernelChoice &k, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t stream)
 {
-    dim3 grid(grid_for(a.n, compute_units)), block(kBlock);
-    // variant 0: generic kernel (every kind, ocml math) — the A/B baseline;
-    // variant 1: tuned table kernel; a single-material GGX launch has no table path and stays generic
-    const bool tuned = variant >= 1 && (multi || a.single.kind != KIND_GGX);
-    if (variant >= 1 && !multi && a.single.kind == KIND_GGX) {     // tuned analytic kernel
-        hipLaunchKernelGGL((k_ggx<MODE, true>), grid, block, 0, stream, a);
-        return hipGetLastError();
-    }
-    if (variant >= 1 && multi && has_ggx && !has_table) {          // a batch over analytic materials only
-        hipLaunchKernelGGL((k_ggx<MODE, true, true>), grid, block, 0, stream, a);
-        return hipGetLastError();
-    }
-    if constexpr (MODE != MODE_PDF) {
-        // variant 3: cooperative LDS-DMA brick fetch (brick layout + trilinear only; otherwise variant 2)
-        if (tuned && variant >= 3 && layout == LAYOUT_BRICK && a.opts.lookup == 1) {
-            // 64 KB (two lookups) or 32 KB (one) of LDS per 256-thread block: 2 or 4 blocks per CU, whole rounds over the XCDs
-            const dim3 g(dma_grid<MODE>(a.n, compute_units, true)), b(kDmaBlock);
-            if (multi && has_ggx)      MRL_DMA_LAUNCH(true, true, false);
-            else if (multi)            MRL_DMA_LAUNCH(true, false, false);
-            else                       MRL_DMA_LAUNCH(false, false, false);
-            return hipGetLastError();
-        }
-    }
-    // (k_table blends the texels as stored: a renormalising context's nearest lookups / rows-layout tables take the generic kernel)
-    if (tuned && a.opts.negative != NEGATIVE_RENORMALISE) {
-        launch_table<MODE>(a, multi, variant >= 2, a.opts.lookup, layout, grid, block, stream);
-    } else {
-        if (multi) hipLaunchKernelGGL((k_batch<MODE, true>), grid, block, 0, stream, a);
-        else       hipLaunchKernelGGL((k_batch<MODE, false>), grid, block, 0, stream, a);
+    switch (k.family) {
+    case KERNEL_GGX:
+        with_flags([&](auto per_lane, auto indexed) { hipLaunchKernelGGL((k_ggx<MODE, true, per_lane, indexed>), grid, block, 0, stream, a); },
+                   k.multi, k.indexed);
+        break;
+    case KERNEL_TABLE_DMA:
+        with_flags([&](auto multi, auto ggx, auto indexed, auto standard) {
+            if constexpr (MODE != MODE_PDF && (multi || !ggx))
+                hipLaunchKernelGGL((k_table_dma<MODE, multi, true, ggx, indexed, standard>), grid, block, 0, stream, a);
+        }, k.multi, k.ggx, k.indexed, k.standard);
+        break;
+    case KERNEL_TABLE:
+        with_flags([&](auto multi, auto nt, auto trilinear, auto brick) {
+            hipLaunchKernelGGL((k_table<MODE, multi, nt, trilinear ? 1 : 0, brick ? LAYOUT_BRICK : LAYOUT_ROWS>), grid, block, 0, stream, a);
+        }, k.multi, k.nt, k.lookup != 0, k.layout == LAYOUT_BRICK);
+        break;
+    default:
+        with_flags([&](auto multi, auto indexed) { hipLaunchKernelGGL((k_batch<MODE, multi, indexed>), grid, block, 0, stream, a); }, k.multi, k.indexed);
     }
     return hipGetLastError();
 }
 
 } // namespace
 
-hipError_t launch_batch(int mode, const BatchArgs &a, bool multi, int variant, int layout, bool has_ggx, bool has_table, int compute_units, hipStream_t stream)
+KernelChoice route_batch(int mode, const BatchArgs &a, const BatchRoute &r)
+{
+    const bool multi = a.mat != nullptr, indexed = a.idx != nullptr;
+    const int v = indexed ? 3 : r.variant;
+    KernelChoice k = { KERNEL_BATCH, mode, multi, indexed, false, 0, 0, false, false, kBlock, 8, false };
+    if (v >= 1 && !multi && a.single.kind == KIND_GGX) {
+        k.family = KERNEL_GGX;
+    } else if (v >= 1 && multi && r.has_ggx && !r.has_table) {
+        k.family = KERNEL_GGX;
+    } else if (mode != MODE_PDF && v >= 3 && r.layout == LAYOUT_BRICK && a.opts.lookup == 1) {
+        k.family = KERNEL_TABLE_DMA;
+        k.ggx = multi && r.has_ggx;
+        k.standard = a.any_standard || a.opts.negative == NEGATIVE_RENORMALISE;
+        k.block = kDmaBlock; k.blocks_per_cu = dma_blocks_per_cu(mode); k.whole_xcds = r.whole_xcds;
+    } else if (!indexed && v >= 1 && a.opts.negative != NEGATIVE_RENORMALISE) {
+        k.family = KERNEL_TABLE;
+        k.nt = v >= 2; k.lookup = a.opts.lookup ? 1 : 0; k.layout = r.layout == LAYOUT_BRICK ? LAYOUT_BRICK : LAYOUT_ROWS;
+    }
+    return k;
+}
+
+std::string kernel_name(const KernelChoice &k)
+{
+    auto b = [](bool x) { return x ? "true" : "false"; };
+    char s[96];
+    switch (k.family) {
+    case KERNEL_GGX:       snprintf(s, sizeof s, "k_ggx<%d, true, %s, %s>", k.mode, b(k.multi), b(k.indexed)); break;
+    case KERNEL_TABLE_DMA: snprintf(s, sizeof s, "k_table_dma<%d, %s, true, %s, %s, %s>", k.mode, b(k.multi), b(k.ggx), b(k.indexed), b(k.standard)); break;
+    case KERNEL_TABLE:     snprintf(s, sizeof s, "k_table<%d, %s, %s, %d, %d>", k.mode, b(k.multi), b(k.nt), k.lookup, k.layout); break;
+    default:               snprintf(s, sizeof s, "k_batch<%d, %s, %s>", k.mode, b(k.multi), b(k.indexed));
+    }
+    return s;
+}
+
+hipError_t launch_batch(int mode, const BatchArgs &a, const BatchRoute &r, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    return with_mode(mode, [&](auto m) {
-        return launch_mode<decltype(m)::value>(a, multi, variant, layout, has_ggx, has_table, compute_units, stream);
-    });
+    const KernelChoice k = route_batch(mode, a, r);
+    const dim3 grid(grid_blocks(a.n, (size_t)k.block, (size_t)compute_units * k.blocks_per_cu, k.whole_xcds)), block(k.block);
+    return with_mode(mode, [&](auto m) { return launch_choice<decltype(m)::value>(k, a, grid, block, stream); });
 }
 
 void partition_geometry(size_t n, int compute_units, uint32_t *segments, uint32_t *seg_len)
@@ -986,72 +987,6 @@ hipError_t launch_partition_kinds(const int32_t *mat, size_t n, const MaterialDe
     hipLaunchKernelGGL(k_partition_kinds, dim3(segments), dim3(kBlock), 0, stream, mat, n, materials, n_materials,
                        queue_table, queue_ggx, offsets, seg_len);
     return hipGetLastError();
-}
-
-namespace {
-template <int MODE>
-hipError_t launch_queue_mode(const BatchArgs &a, bool ggx_queue, int compute_units, hipStream_t stream)
-{
-    if constexpr (MODE == MODE_PDF) {
-        return hipErrorInvalidValue;
-    } else {
-        if (ggx_queue) {
-            hipLaunchKernelGGL((k_ggx<MODE, true, true, true>), dim3(grid_for(a.n, compute_units)), dim3(kBlock), 0, stream, a);
-        } else {
-            // not rounded to whole XCD rounds, unlike the other two DMA grids: block_map applies here only when the capped grid is a multiple of 8
-            const dim3 g(dma_grid<MODE>(a.n, compute_units, false)), b(kDmaBlock);
-            MRL_DMA_LAUNCH(true, false, true);
-        }
-        return hipGetLastError();
-    }
-}
-} // namespace
-
-// one kind's dense queue (a.idx, a.idx_count) of a partitioned mixed batch; a.n = units of the whole batch (grid sizing)
-hipError_t launch_batch_queue(int mode, const BatchArgs &a, bool ggx_queue, int compute_units, hipStream_t stream)
-{
-    if (a.n == 0) return hipSuccess;
-    return with_mode(mode, [&](auto m) { return launch_queue_mode<decltype(m)::value>(a, ggx_queue, compute_units, stream); });
-}
-
-namespace {
-template <int MODE>
-hipError_t launch_indexed_mode(const BatchArgs &a, bool multi, int layout, bool has_ggx, bool has_table, int compute_units, hipStream_t stream)
-{
-    const dim3 grid(grid_for(a.n, compute_units)), block(kBlock);
-    if (!multi && a.single.kind == KIND_GGX) {
-        hipLaunchKernelGGL((k_ggx<MODE, true, false, true>), grid, block, 0, stream, a);
-        return hipGetLastError();
-    }
-    if (multi && has_ggx && !has_table) {
-        hipLaunchKernelGGL((k_ggx<MODE, true, true, true>), grid, block, 0, stream, a);
-        return hipGetLastError();
-    }
-    if constexpr (MODE != MODE_PDF) {
-        if (layout == LAYOUT_BRICK && a.opts.lookup == 1) {
-            const dim3 g(dma_grid<MODE>(a.n, compute_units, true)), b(kDmaBlock);
-            if (multi && has_ggx)      MRL_DMA_LAUNCH(true, true, true);
-            else if (multi)            MRL_DMA_LAUNCH(true, false, true);
-            else                       MRL_DMA_LAUNCH(false, false, true);
-            return hipGetLastError();
-        }
-    }
-    // rows layout, nearest lookup, pdf: the generic kernel walks the queue
-    if (multi) hipLaunchKernelGGL((k_batch<MODE, true, true>), grid, block, 0, stream, a);
-    else       hipLaunchKernelGGL((k_batch<MODE, false, true>), grid, block, 0, stream, a);
-    return hipGetLastError();
-}
-} // namespace
-
-// A caller's wavefront queue: units a.idx[0 .. min(*a.idx_count, a.n)) of the arrays in `a`; a.n is the queue's
-// capacity (grid sizing and an upper clamp on the device-side count).
-hipError_t launch_batch_indexed(int mode, const BatchArgs &a, bool multi, int layout, bool has_ggx, bool has_table,
-                                int compute_units, hipStream_t stream)
-{
-    if (a.n == 0) return hipSuccess;
-    return with_mode(mode, [&](auto m) {
-        return launch_indexed_mode<decltype(m)::value>(a, multi, layout, has_ggx, has_table, compute_units, stream);
-    });
 }
 
 void material_partition_geometry(size_t n, int compute_units, uint32_t *chunks, uint32_t *chunk_len)

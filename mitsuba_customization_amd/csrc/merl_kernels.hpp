@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -60,7 +61,8 @@ struct BatchArgs {
     int any_standard;                // some table this launch may meet is in a standard parameterisation (MaterialDev::param != 0)
     int block_map;                   // k_table_dma: 0 interleaved grid-stride tiles, 1 one contiguous eighth of the batch per XCD
     Options opts;
-    // queue launches: a queue of unit indices (a caller's wavefront queue, or one kind's queue built by k_partition_kinds)
+    // queue launches (idx != nullptr): the units idx[0 .. min(*idx_count, n)) — a caller's wavefront queue (n: its capacity) or one
+    // kind's queue built by k_partition_kinds (n: the units of the whole batch); n sizes the grid and clamps the device-side count
     const uint32_t *idx;
     const uint32_t *idx_count;               // its length, in device memory
 };
@@ -98,21 +100,54 @@ template <bool INDEXED> __device__ __forceinline__ size_t item_count(const Batch
     else return a.n;
 }
 
-// mode: a Mode (MODE_EVAL .. MODE_EVAL_PDF)
-// variant: MRL_OPT_KERNEL (0 generic, 1 tuned table path, 2 + non-temporal streams, 3 + LDS-DMA brick fetch; 4 is handled by the caller)
-// layout: the context-wide table layout (every table of a context has the same one)
-// has_ggx / has_table: the context holds at least one analytic (GGX) / one table material, i.e. what a mixed batch may contain
-hipError_t launch_batch(int mode, const BatchArgs &a, bool multi, int variant, int layout, bool has_ggx, bool has_table, int compute_units, hipStream_t stream);
-// kind-partitioned mixed batches (MRL_OPT_KERNEL >= 4): build the two queues, then run one of them
+// ---- which kernel serves a batch launch ----
+// What the choice depends on beyond BatchArgs (a.mat: a material id per unit, a.idx: the launch walks a queue).
+struct BatchRoute {
+    int variant;                     // MRL_OPT_KERNEL: 0 generic, 1 tuned table path, 2 + non-temporal streams, 3 + LDS-DMA brick fetch, 4 + kind partition
+    int layout;                      // the context-wide table layout (every table of a context has the same one)
+    bool has_ggx, has_table;         // what a batch with material ids may contain: analytic (GGX) / table materials
+    bool whole_xcds;                 // k_table_dma's grid is rounded up to whole rounds over the 8 XCDs
+};
+// One kernel instantiation and its grid: grid_blocks(a.n, block, compute units * blocks_per_cu, whole_xcds) blocks of `block` threads.
+enum KernelFamily : int { KERNEL_BATCH = 0, KERNEL_TABLE = 1, KERNEL_TABLE_DMA = 2, KERNEL_GGX = 3 };
+struct KernelChoice {
+    int family, mode;
+    bool multi;                      // MULTI (k_ggx: PER_LANE): the material comes from a.mat
+    bool indexed;                    // INDEXED (k_table has no queue form)
+    bool nt;                         // k_table: NT
+    int lookup, layout;              // k_table: LOOKUP, LAYOUT
+    bool ggx, standard;              // k_table_dma: GGX, STD
+    int block, blocks_per_cu;
+    bool whole_xcds;
+};
+// Pure arithmetic, no HIP call.  The first rule that matches, with V = r.variant for whole arrays and 3 for a queue (queues ignore
+// MRL_OPT_KERNEL), multi = a.mat != nullptr, indexed = a.idx != nullptr:
+//   1. V >= 1, a single GGX material                              k_ggx<M, true, false, indexed>       tuned analytic kernel
+//   2. V >= 1, multi, has_ggx, no table                           k_ggx<M, true, true, indexed>        ... over several analytic materials
+//   3. M != PDF, V >= 3, brick layout, trilinear lookup           k_table_dma<M, multi, true, multi && has_ggx, indexed, STD>
+//        STD: a.any_standard or the renormalising blend; its LDS lets a CU hold 2 (fused mode) or 4 blocks
+//   4. whole arrays, V >= 1, not the renormalising blend          k_table<M, multi, V >= 2, lookup, layout>   (blends the texels as stored)
+//   5. otherwise                                                  k_batch<M, multi, indexed>           generic: every kind, ocml f64 math
+KernelChoice route_batch(int mode, const BatchArgs &a, const BatchRoute &r);
+// the kernel's name as the code object spells it (demangled, without namespaces and arguments): "k_table_dma<3, false, true, false, false, false>"
+std::string kernel_name(const KernelChoice &k);
+// MRL_OPT_KERNEL >= 4: a whole-array batch that may mix table and analytic materials is split into one dense queue per kind
+// (launch_partition_kinds), and each queue runs as a queue launch of kind_queue_route: k_table_dma without the GGX code (the one
+// DMA grid that is not rounded to whole XCD rounds: block_map applies there only when the capped grid is a multiple of 8), k_ggx.
+inline bool route_partitions(int mode, const BatchArgs &a, const BatchRoute &r)
+{
+    return !a.idx && a.mat && r.has_ggx && r.has_table && r.variant >= 4 && mode != MODE_PDF && r.layout == LAYOUT_BRICK && a.opts.lookup == 1 &&
+           a.n < ((size_t)1 << 32);
+}
+inline BatchRoute kind_queue_route(const BatchRoute &r, bool ggx_queue) { return { r.variant, r.layout, ggx_queue, !ggx_queue, false }; }
+// launches the kernel route_batch names
+hipError_t launch_batch(int mode, const BatchArgs &a, const BatchRoute &r, int compute_units, hipStream_t stream);
+// kind-partitioned mixed batches: build the two queues (a.idx / a.idx_count of the two queue launches; a.n stays the whole batch)
 void partition_geometry(size_t n, int compute_units, uint32_t *segments, uint32_t *seg_len);
 // work: 4*segments + 2 uint32 (counts, offsets, totals[2] at work + 4*segments)
 hipError_t launch_partition_kinds(const int32_t *mat, size_t n, const MaterialDev *materials, int n_materials,
                                   uint32_t *queue_table, uint32_t *queue_ggx, uint32_t *work,
                                   uint32_t segments, uint32_t seg_len, hipStream_t stream);
-hipError_t launch_batch_queue(int mode, const BatchArgs &a, bool ggx_queue, int compute_units, hipStream_t stream);
-// a caller's wavefront queue (mrl_*_queue): units a.idx[0 .. min(*a.idx_count, a.n)), a.n = the queue's capacity
-hipError_t launch_batch_indexed(int mode, const BatchArgs &a, bool multi, int layout, bool has_ggx, bool has_table,
-                                int compute_units, hipStream_t stream);
 // per-material compaction for wavefront callers (mrl_partition_by_material): stable partition of [0, n) by material id
 constexpr int kMaxPartitionMaterials = 2048;
 void material_partition_geometry(size_t n, int compute_units, uint32_t *chunks, uint32_t *chunk_len);
@@ -133,7 +168,7 @@ hipError_t launch_build_sampling2d(const MaterialDev &m, const Options &opts, in
 constexpr int kMaxChannels = 32;
 // nch_brick_float4s(n_ch): float4s per cell: 2 (1 ch), 4 (2 ch), 8 * ceil(n_ch / 4)  (merl_image_file.hpp)
 // mode: any but MODE_PDF (pdf alone: the RGB pdf kernel serves every table kind)
-hipError_t launch_batch_nch(int mode, const BatchArgs &a, bool multi, int n_ch, int compute_units, hipStream_t stream);
+hipError_t launch_batch_nch(int mode, const BatchArgs &a, int n_ch, int compute_units, hipStream_t stream);
 hipError_t launch_build_table_nch(const double *d_planar, const double *d_scale, const int dims[3], int n_ch, int param, int clamp, float4 *d_out,
                                   int compute_units, hipStream_t stream);
 // ---- the adaptive-parameterisation measured BSDF (merl_rgl.hip; RGL *.bsdf) ----
@@ -143,16 +178,16 @@ const char *rgl_check_fields(const RglFields &f);                        // null
 RglLayout rgl_build_image(const RglFields &f, std::vector<float> &blob); // normalised tables + running integrals, host f64
 RglDev rgl_descriptor(const RglFields &f, const RglLayout &l, const float *base);
 // r != nullptr: a single-material launch; r == nullptr: a batch with material ids (a.mat) — the units whose id names an RGL material
-// are evaluated and written, every other unit is left as it is.  indexed: walk the queue a.idx / a.idx_count.
+// are evaluated and written, every other unit is left as it is.  a.idx != nullptr: walk the queue a.idx / a.idx_count.
 // search (MRL_OPT_RGL_SEARCH): 0 = a single-material launch reads the distributions' search tables from a copy in LDS when they fit
 // a CU's LDS, 1 = always from memory (the results are the same bits)
-hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream);
+hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, int search, int compute_units, hipStream_t stream);
 // a spectral RGL material: a.out_rgb / a.out_weight hold n x W values at the per-unit wavelengths wl [n][W] (nullptr: the file's own
 // wavelength nodes, W = their number); single material, whole arrays
 hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream);
-// the same over a queue (indexed: a.idx / a.idx_count, a.n = the capacity) and / or with a material id per unit (r == nullptr: a.mat,
+// the same over a queue (a.idx != nullptr: a.idx / a.idx_count, a.n = the capacity) and / or with a material id per unit (r == nullptr: a.mat,
 // a.materials; a unit whose id names no live spectral RGL material gets zeros in every output of the mode); any mode but MODE_PDF
-hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, bool indexed, const float *wl, int W, int search, int compute_units,
+hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, const float *wl, int W, int search, int compute_units,
                                  hipStream_t stream);
 // ---- one-unit calls (merl_scalar.hip): a bounded-lifetime service kernel answers requests posted in pinned host memory ----
 struct ScalarBoard;

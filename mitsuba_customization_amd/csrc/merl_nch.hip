@@ -426,11 +426,11 @@ hipError_t launch_nch_mode(const BatchArgs &a, bool multi, bool indexed, int n_c
 
 } // namespace
 
-hipError_t launch_batch_nch(int mode, const BatchArgs &a, bool multi, int n_ch, int compute_units, hipStream_t stream)
+hipError_t launch_batch_nch(int mode, const BatchArgs &a, int n_ch, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
     if (n_ch < 1 || n_ch > kMaxChannels || n_ch == 3) return hipErrorInvalidValue;
-    const bool indexed = a.idx != nullptr;                     // a caller's wavefront queue (a.n = its capacity)
+    const bool multi = a.mat != nullptr, indexed = a.idx != nullptr;      // ids per unit; a caller's wavefront queue (a.n = its capacity)
     return with_mode(mode, [&](auto m) { return launch_nch_mode<decltype(m)::value>(a, multi, indexed, n_ch, compute_units, stream); });
 }
 

@@ -748,10 +748,10 @@ hipError_t launch_spectral_queue_mode(const BatchArgs &a, const RglDev *r, bool 
 
 } // namespace
 
-hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, bool indexed, const float *wl, int W, int search, int compute_units,
-                                 hipStream_t stream)
+hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
+    const bool indexed = a.idx != nullptr;
     return with_mode(mode, [&](auto m) -> hipError_t {
         constexpr int M = decltype(m)::value;
         if constexpr (M == MODE_PDF) return hipErrorInvalidValue;       // (the pdf is wavelength-free: the RGB pdf calls serve these materials)
@@ -765,9 +765,10 @@ hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, co
     return with_mode(mode, [&](auto m) { return launch_spectral_mode<decltype(m)::value>(a, r, wl, W, search, compute_units, stream); });
 }
 
-hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream)
+hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, int search, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
+    const bool indexed = a.idx != nullptr;
     // The fused unit of a file whose integrals do not fit a CU's LDS (an anisotropic file: its lookups blend four slices of a 45 MB
     // image, the launch waits on L1 fills): eval + pdf and sample() as TWO launches on the stream.  The fused kernel carries sample()'s
     // 220 VGPRs through its eval as well (2 waves per SIMD); apart, eval + pdf runs at 3 waves per SIMD and sample() with its marginal

@@ -64,7 +64,7 @@ ABI_SYMBOLS = (
     "mrl_group_material_upload_rgl_spectral",
     "mrl_eval_spectral_queue", "mrl_eval_pdf_spectral_queue", "mrl_sample_spectral_queue", "mrl_eval_sample_spectral_queue",
     "mrl_eval_spectral_batch_mat", "mrl_eval_pdf_spectral_batch_mat", "mrl_sample_spectral_batch_mat", "mrl_eval_sample_spectral_batch_mat",
-    "mrl_table_grad_batch",
+    "mrl_table_grad_batch", "mrl_batch_route",
 )
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
@@ -165,6 +165,14 @@ class PlanOp(C.Structure):
 
 
 PLAN_COMPUTE, PLAN_TRANSFER = 0, 1
+
+
+class RouteLaunch(C.Structure):
+    """mrl_route_launch: one kernel launch of an RGB call (include/merl_hip.h)."""
+    _fields_ = [("kernel", C.c_char * 64), ("block", C.c_int), ("blocks_per_cu", C.c_int), ("whole_xcds", C.c_int)]
+
+
+ROUTE_ONE_TABLE, ROUTE_ONE_GGX, ROUTE_IDS = 0, 1, 2
 
 
 class LinkReport(C.Structure):
@@ -326,6 +334,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_group_last_timing.argtypes = [vp, C.POINTER(C.c_float)]
     L.mrl_group_plan.argtypes = [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(PlanOp), C.c_size_t]; L.mrl_group_plan.restype = C.c_size_t
     L.mrl_group_link_test.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(LinkReport)]
+    L.mrl_batch_route.argtypes = [C.c_int] * 10 + [C.c_size_t, C.POINTER(RouteLaunch), C.c_size_t]; L.mrl_batch_route.restype = C.c_size_t
     if path is None:
         _lib = L
     return L
@@ -897,6 +906,16 @@ def group_plan(n_total: int, world: int, chunk: int, root: int):
     got = L.mrl_group_plan(n_total, world, chunk, root, ops, n)
     assert got == n
     return [ops[i] for i in range(n)]
+
+
+def batch_route(mode: int, variant: int, layout: int, lookup: int, negative: int, any_standard: int, material: int, queued: int,
+                has_ggx: int, has_table: int, n: int):
+    """mrl_batch_route: the kernels one RGB call launches, in order, as (name, block, blocks_per_cu, whole_xcds) (pure arithmetic: needs no GPU)."""
+    L = load_library()
+    out = (RouteLaunch * 8)()
+    got = L.mrl_batch_route(mode, variant, layout, lookup, negative, any_standard, material, queued, has_ggx, has_table, n, out, 8)
+    assert got <= 8
+    return [(out[i].kernel.decode(), out[i].block, out[i].blocks_per_cu, bool(out[i].whole_xcds)) for i in range(got)]
 
 
 class MerlGroup:

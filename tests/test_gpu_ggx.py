@@ -14,7 +14,7 @@ Comparison rules, every unit of every case, no ignored fraction:
     must lie inside [min, max] of the oracle's pdf(wi, wo') and eval(wi, wo') / pdf(wi, wo') over the returned wo' and its
     one-ulp neighbours, widened by 2e-6 relative (ggx_reference.envelope; the oracle's own samples satisfy it).
   * sample at alpha >= 0.1, additionally: pdf2 within 2e-6 and weight within 1e-6 of the oracle's sample().
-Which paths must agree bit for bit follows the dispatch (merl_kernels.hip, launch_mode): the tuned functions of
+Which paths must agree bit for bit follows the dispatch (route_batch, csrc/merl_kernels.hpp): the tuned functions of
 merl_ggx_fast.hpp serve single-material calls under variants 1-4 (k_ggx), every queue call, GGX-only id batches
 (k_ggx<PER_LANE>), mixed batches under variant 3 (ggx_lane in k_table_dma) and 4 (k_ggx<INDEXED> behind the kind partition)
 and the one-unit service; the generic functions of merl_device.hpp serve variant 0 (k_batch) and the GGX lanes of a mixed

@@ -2,11 +2,9 @@
 kernel, sampler and entry point, at shapes the other table tests never build: single-cell axes, no power of two, more theta_h bins
 than k_sampling2d_scan has threads.  Everything is compared with oracle/merl_oracle.c on generate_pairs units plus units aimed at the
 first and last cell of every axis (_targeted), and every entry point with the fused call bit for bit.  Which kernels a case reaches
-follows launch_mode / launch_indexed_mode / launch_build_sampling2d (csrc/merl_kernels.hip) and launch_nch_cpad (csrc/merl_nch.hip):
-  * MRL_OPT_KERNEL 0: k_batch<M, false>; 1: k_table<M, ., false, LOOKUP, LAYOUT>; 2: k_table<M, ., true, LOOKUP, LAYOUT>;
-    3 and 4, bricks and trilinear: k_table_dma<M, false, ...> (byte offsets in 32 bits: every case here is below 2^25 cells),
-    rows or nearest: k_table<M, ., true, ...>.  pdf() (MODE_PDF) never takes k_table_dma;
-  * queues: k_table_dma<M, ., ., ., true> for bricks and trilinear, k_batch<M, ., true> otherwise;
+follows route_batch (csrc/merl_kernels.hpp; tests/test_route_cpu.py checks it on the CPU), launch_build_sampling2d
+(csrc/merl_kernels.hip) and launch_nch_cpad (csrc/merl_nch.hip):
+  * MRL_OPT_KERNEL 0 .. 4 and queues: k_batch, k_table, k_table_dma (byte offsets in 32 bits: every case here is below 2^25 cells);
     a batch with material ids under variant 4 first partitions the units by kind (k_count_kinds, k_partition_kinds);
   * upload: k_build_bricks or k_build_rows, then k_sampling2d_mass<LAYOUT> + k_sampling2d_scan (the conditional table).
     n_th = 257, 512 and 777 give each of the scan's 256 threads 2, 2 and 4 (ragged: 777 = 256 * 3 + 9) theta_h bins;
