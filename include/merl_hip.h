@@ -519,6 +519,9 @@ size_t mrl_batch_route(int mode, int variant, int layout, int lookup, int negati
 int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                          int32_t id, size_t n, double *grad_planar);
 
+/* ---- fitting a GGX conductor: the parameter gradient of eval ----
+ * mrl_ggx_grad_batch is declared in merl_hip_fit.h, which includes this header. */
+
 /* ---- synthetic inputs, generated in place on the device; device pointers only ---- */
 int mrl_generate_pairs(mrl_ctx *ctx, uint64_t seed, uint64_t first_index, size_t n,
                        float *wi, float *wo, float *u);

@@ -33,7 +33,7 @@ def _newer(target: str, sources) -> bool:
 
 def lib_sources():
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    deps = srcs + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(ROOT, "include", "merl_hip.h")]
+    deps = srcs + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))
     return srcs, deps
 
 

@@ -7,6 +7,7 @@
 //   merl_image_cache.hip   on-disk cache of a material's device image
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
 //   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
+//   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
 #pragma once
 #include "../../include/merl_hip.h"
 
@@ -109,7 +110,8 @@ struct mrl_ctx {
     //   BUF_QUEUES       kind-partitioned mixed batches: [2][n] unit indices + partition work area behind them
     //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
     //   BUF_GRAD_BRICKS  mrl_table_grad_batch: gradient bricks, one 256-B record per table cell (merl_table_grad.hip)
-    enum { BUF_STAGE, BUF_QUEUES, BUF_PART_WORK, BUF_GRAD_BRICKS, BUF_COUNT };
+    //   BUF_GGX_GRAD     mrl_ggx_grad_batch: one 256-B row of partial sums per block + the sums of a host-array call (merl_ggx_grad.hip)
+    enum { BUF_STAGE, BUF_QUEUES, BUF_PART_WORK, BUF_GRAD_BRICKS, BUF_GGX_GRAD, BUF_COUNT };
     DeviceBuf buf[BUF_COUNT];
     int table_grad_kernel = 0;       // MRL_OPT_TABLE_GRAD_KERNEL
     std::vector<MaterialHost> materials;

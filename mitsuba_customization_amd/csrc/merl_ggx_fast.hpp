@@ -15,7 +15,7 @@ struct GgxConsts {                 // per material, computed once per launch (SG
     double alpha, inv_alpha2, inv_pi_alpha2;
     double eta2_k2[3];             // eta^2 - k^2
     double four_k2_eta2[3];        // 4 k^2 eta^2
-    __device__ __forceinline__ explicit GgxConsts(const MaterialDev &m)
+    MRL_HD explicit GgxConsts(const MaterialDev &m)
     {
         alpha = m.alpha;
         inv_alpha2 = rcp_nr(m.alpha * m.alpha);
@@ -63,7 +63,7 @@ __device__ __forceinline__ double fresnel_conductor(const GgxConsts &g, int ch, 
     return 0.5 * (rp2 + rs2);
 }
 
-__device__ __forceinline__ Vec3 unit_sum(const Vec3 &a, const Vec3 &b)
+MRL_HD Vec3 unit_sum(const Vec3 &a, const Vec3 &b)
 {
     const double x = a.x + b.x, y = a.y + b.y, z = a.z + b.z;
     double s, rs;
@@ -84,6 +84,101 @@ __device__ __forceinline__ void ggx_eval_pdf(const GgxConsts &g, const Vec3 &in,
     rgb[0] = D == 0.0 ? 0.0 : fresnel_conductor(g, 0, c) * model;
     rgb[1] = D == 0.0 ? 0.0 : fresnel_conductor(g, 1, c) * model;
     rgb[2] = D == 0.0 ? 0.0 : fresnel_conductor(g, 2, c) * model;
+}
+
+// ---- forward-mode twins of ggx_D, ggx_G1 and fresnel_conductor (merl_ggx_grad.hip) ----
+// Each returns the value its twin returns (same selects) and the derivative the parameter gradient needs, from the reciprocals
+// and square roots the value takes anyway.  The alpha-derivatives are LOG-derivatives: d eval / d alpha = eval x their sum, so
+// nothing is divided by a D or G1 that vanishes.  Contraction is off: the gradient-only and the gradient + normal kernel inline
+// these in different surroundings and must round alike (mrl_ggx_grad_batch returns the same grad_params bits with and without
+// `normal`); every fused multiply-add below is spelt out.
+
+// root = sin^2/a^2 + cos^2, D = 1 / (pi a^2 root^2):  d ln D / d alpha = -2/a + 4 sin^2 / (a^3 root) = (2/a) (sin^2/a^2 - cos^2) / root
+MRL_HD double ggx_D_dlog(const GgxConsts &g, const Vec3 &m, double &dlog)
+{
+#pragma clang fp contract(off)
+    const double s_a2 = __builtin_fma(m.x, m.x, m.y * m.y) * g.inv_alpha2, c2 = m.z * m.z;
+    const double inv = rcp_nr(__builtin_fmax(s_a2 + c2, kTiny));
+    const double r = g.inv_pi_alpha2 * (inv * inv);
+    dlog = 2.0 * (g.alpha * g.inv_alpha2) * ((s_a2 - c2) * inv);
+    return (m.z <= 0.0 || r * m.z < 1e-20) ? 0.0 : r;
+}
+
+// q = sqrt(vz^2 + a^2 sin^2), G1 = 2 |vz| / (|vz| + q):  d ln G1 / d alpha = -(a sin^2 / q) / (|vz| + q)
+MRL_HD double ggx_G1_dlog(const GgxConsts &g, const Vec3 &v, const Vec3 &m, double &dlog)
+{
+#pragma clang fp contract(off)
+    const double vm = __builtin_fma(v.x, m.x, __builtin_fma(v.y, m.y, v.z * m.z));
+    const double vz2 = v.z * v.z;
+    const double s2 = 1.0 - vz2;
+    const double az = __builtin_fabs(v.z);
+    double q, rq;
+    sqrt_rsqrt(__builtin_fma(g.alpha * g.alpha, s2, vz2), q, rq);
+    const double inv = rcp_nr(__builtin_fmax(az + q, kTiny));
+    const bool flat = s2 <= 0.0;
+    dlog = flat ? 0.0 : -(g.alpha * s2) * (rq * inv);
+    const double res = flat ? 1.0 : 2.0 * az * inv;
+    return vm * v.z <= 0.0 ? 0.0 : res;
+}
+
+// F and its derivatives with respect to E = eta^2 - k^2 (GgxConsts::eta2_k2) and Q = 4 k^2 eta^2 (four_k2_eta2); the caller's
+// chain rule is dF/d eta = 2 eta F_E + 8 k^2 eta F_Q, dF/dk = -2 k F_E + 8 k eta^2 F_Q.
+// With A = sqrt(t1^2 + Q) and a = sqrt((A + t1) / 2):  A_E = t1 / A, A_Q = 1 / (2 A), a_E = a / (2 A), a_Q = 1 / (8 A a);
+// Rs = (T1 - T2) / (T1 + T2) gives dRs = 2 (T2 dT1 - T1 dT2) / (T1 + T2)^2, likewise P = (T3 - T4) / (T3 + T4); F = Rs (1 + P) / 2.
+MRL_HD double fresnel_conductor_d(const GgxConsts &g, int ch, double c, double &dE, double &dQ)
+{
+#pragma clang fp contract(off)
+    const double c2 = c * c, s2 = 1.0 - c2, s4 = s2 * s2;
+    const double t1 = g.eta2_k2[ch] - s2;
+    double A, rA, a, ra;
+    sqrt_rsqrt(__builtin_fma(t1, t1, g.four_k2_eta2[ch]), A, rA);
+    sqrt_rsqrt(0.5 * (A + t1), a, ra);
+    const double term1 = A + c2, term2 = 2.0 * a * c;
+    const double term3 = __builtin_fma(A, c2, s4), term4 = term2 * s2;
+    const double d12 = term1 + term2, d34 = term3 + term4;
+    const double inv = rcp_nr(d12 * d34);
+    const double inv12 = d34 * inv, inv34 = d12 * inv;
+    const double rs = (term1 - term2) * inv12, p1 = 1.0 + (term3 - term4) * inv34;
+    const double k12 = 2.0 * (inv12 * inv12) * p1, k34 = 2.0 * (inv34 * inv34) * rs;
+    const double two_c = 2.0 * c;
+    // dT1 = dA, dT2 = 2 c da, dT3 = c^2 dA, dT4 = 2 c s2 da
+    const double A_E = t1 * rA, A_Q = 0.5 * rA, a_E = 0.5 * (a * rA), a_Q = 0.125 * (rA * ra);
+    const double t2_E = two_c * a_E, t2_Q = two_c * a_Q;
+    dE = 0.5 * __builtin_fma(k12, __builtin_fma(term2, A_E, -(term1 * t2_E)), k34 * __builtin_fma(term4 * c2, A_E, -(term3 * s2 * t2_E)));
+    dQ = 0.5 * __builtin_fma(k12, __builtin_fma(term2, A_Q, -(term1 * t2_Q)), k34 * __builtin_fma(term4 * c2, A_Q, -(term3 * s2 * t2_Q)));
+    return 0.5 * (rs * p1);
+}
+
+// eval of one pair of unit directions and its Jacobian J[c] = d eval_c / d (alpha, eta_c, k_c) at the material's parameters.
+// live == false: one of eval's own D / G1 selects returned 0 (the values are then not to be used)
+struct GgxJacobian {
+    double d_alpha[3], d_eta[3], d_k[3];
+    bool live;
+};
+MRL_HD GgxJacobian ggx_eval_jacobian(const GgxConsts &g, const double eta[3], const double k[3], const Vec3 &in, const Vec3 &out)
+{
+#pragma clang fp contract(off)
+    const Vec3 m = unit_sum(in, out);
+    double lD, lGi, lGo;
+    const double D = ggx_D_dlog(g, m, lD);
+    const double G1i = ggx_G1_dlog(g, in, m, lGi);
+    const double G1o = ggx_G1_dlog(g, out, m, lGo);
+    const double model = D * G1i * (0.25 * rcp_nr(in.z)) * G1o;
+    const double dlog = lD + lGi + lGo;
+    const double c = __builtin_fma(in.x, m.x, __builtin_fma(in.y, m.y, in.z * m.z));
+    GgxJacobian j;
+    j.live = D != 0.0 && G1i != 0.0 && G1o != 0.0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        double fE, fQ;
+        const double F = fresnel_conductor_d(g, ch, c, fE, fQ);
+        const double e2 = eta[ch] * eta[ch], k2 = k[ch] * k[ch];
+        j.d_alpha[ch] = F * model * dlog;
+        j.d_eta[ch] = model * (2.0 * eta[ch] * __builtin_fma(4.0 * k2, fQ, fE));
+        // F is even in k: at k = 0 the derivative is 0 whatever fE and fQ are
+        j.d_k[ch] = k[ch] == 0.0 ? 0.0 : model * (2.0 * k[ch] * __builtin_fma(4.0 * e2, fQ, -fE));
+    }
+    return j;
 }
 
 // sin / cos of 2 pi u for u in [0,1): only the normal-incidence branch of the sampler needs it.  That branch is taken

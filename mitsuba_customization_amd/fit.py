@@ -1,5 +1,8 @@
-"""From measurements (wi, wo, rgb) to a table: the normalised splat and CGLS on |A T - y|^2, built on MerlHip.eval (A) and
-MerlHip.table_grad (A^T).  numpy arrays in -> numpy out, device tensors in -> device tensors out.
+"""From measurements (wi, wo, rgb) to a material.
+A table: the normalised splat and CGLS on |A T - y|^2, built on MerlHip.eval (A) and MerlHip.table_grad (A^T).  numpy arrays in ->
+numpy out, device tensors in -> device tensors out.
+A GGX conductor (alpha, eta[3], k[3]): Levenberg-Marquardt on sum w (eval - y)^2, built on MerlHip.eval and MerlHip.ggx_grad
+(fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).
 
 The context's lookup / node / cosine options define A.  fit_table uploads iterates that have negative entries, so A is linear
 only with host.OPT_NEGATIVE at keep (1), set before the context's first table is uploaded."""
@@ -80,3 +83,89 @@ def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
     finally:
         ctx.release_material(shape_mid)
     return x, residuals
+
+
+# ---- GGX conductor: Levenberg-Marquardt in q = (ln alpha, ln eta[3], k[3]) ----
+def _ggx_params(q):
+    """p = (alpha, eta[3], k[3]) of q, and dp/dq (diagonal)."""
+    p = np.concatenate([np.exp(q[:4]), q[4:]])
+    return p, np.concatenate([p[:4], np.ones(3)])
+
+
+def lm_ggx(eval_fn, grad_fn, rgb, start, iters, weights=None):
+    """Levenberg-Marquardt on L(p) = sum w (eval(p) - rgb)^2 over p = (alpha, eta[3], k[3]).
+    eval_fn(p) -> eval [n, 3] at the 7-vector p;  grad_fn(p, g, h) -> (sum g J [7], sum h J J^T [7, 7]) as numpy f64, h None = 1;
+    grad_fn is only called right after eval_fn at the same p.  alpha and eta move in log space (the chain rule is applied to the
+    7-vector and the 7 x 7 matrix here), k in linear space, projected onto k >= 0 (a k that starts at 0 stays there; a positive one
+    never lands on 0, where its gradient vanishes).  One eval_fn call per iteration: a step that raises L is dropped and the
+    damping raised.  Returns (alpha, eta [3], k [3], [sqrt(L) at the start and after each iteration])."""
+    alpha, eta, k = start
+    y = _f64(rgb)
+    w = None if weights is None else _f64(weights)
+    if w is not None and w.ndim == 1:
+        w = w[:, None]
+
+    def loss_and_model(q):
+        p, s = _ggx_params(q)
+        r = _f64(eval_fn(p)) - y
+        wr = r if w is None else w * r
+        return float((wr * r).sum()), p, s, wr
+
+    def model(p, s, wr):
+        # g = dL / d eval = 2 w r, h = d2L / d eval2 = 2 w: the factor 2 is applied to the sums
+        h = None if w is None else _f32(w.expand(wr.shape) if host._is_tensor(w) else np.broadcast_to(w, wr.shape))
+        g, N = grad_fn(p, _f32(wr), h)
+        return 2.0 * s * np.asarray(g, np.float64), 2.0 * np.outer(s, s) * np.asarray(N, np.float64)
+
+    q = np.concatenate([np.log(np.asarray([alpha, *eta], np.float64)), np.asarray(k, np.float64)])
+    loss, p, s, wr = loss_and_model(q)
+    grad, N = model(p, s, wr)
+    lam, history = 1e-3, [loss ** 0.5]
+    for _ in range(iters):
+        d = np.diag(N).copy()
+        d[d <= 0.0] = 1.0                                   # a parameter nothing depends on (k of a channel at k = 0) stays put
+        try:
+            step = np.linalg.solve(N + lam * np.diag(d), -grad)
+        except np.linalg.LinAlgError:
+            step = -grad / ((1.0 + lam) * d)
+        trial = q + step
+        # k >= 0.  F depends on k through k^2, so at k = 0 exactly the gradient with respect to k is zero and an iterate that
+        # lands there never leaves: a step that would cross zero from k > 0 stops at a tenth of the current value instead
+        trial[4:] = np.maximum(trial[4:], 0.1 * q[4:])
+        t_loss, t_p, t_s, t_wr = loss_and_model(trial)
+        if np.isfinite(t_loss) and t_loss <= loss:
+            q, loss = trial, t_loss
+            grad, N = model(t_p, t_s, t_wr)
+            lam = max(lam / 10.0, 1e-12)
+        else:
+            lam = min(lam * 10.0, 1e12)
+        history.append(loss ** 0.5)
+    p, _ = _ggx_params(q)
+    return float(p[0]), p[1:4].copy(), p[4:7].copy(), history
+
+
+def fit_ggx(ctx, wi, wo, rgb, start, iters, weights=None):
+    """The GGX conductor closest to the measurements: Levenberg-Marquardt on sum w (eval - rgb)^2 from start = (alpha, eta[3], k[3]).
+    Every iteration creates the material, runs eval and ggx_grad(..., normal=True) on it and releases it.  weights: [n] or [n, 3], None = 1.
+    Returns (alpha, eta [3], k [3], residual history) — see lm_ggx."""
+    held = []
+
+    def drop():
+        while held:
+            ctx.release_material(held.pop())
+
+    def eval_fn(p):
+        drop()
+        held.append(ctx.ggx(float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]]))
+        return ctx.eval(wi, wo, material=held[0])
+
+    def grad_fn(p, g, h):
+        grad, N = ctx.ggx_grad(wi, wo, g, held[0], curvature=h, normal=True)
+        if host._is_tensor(grad):
+            grad, N = grad.cpu().numpy(), N.cpu().numpy()
+        return grad, N
+
+    try:
+        return lm_ggx(eval_fn, grad_fn, rgb, start, iters, weights)
+    finally:
+        drop()

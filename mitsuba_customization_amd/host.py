@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     "mrl_eval_spectral_batch_mat", "mrl_eval_pdf_spectral_batch_mat", "mrl_sample_spectral_batch_mat", "mrl_eval_sample_spectral_batch_mat",
     "mrl_table_grad_batch", "mrl_batch_route",
 )
+# every symbol include/merl_hip_fit.h declares, the fitting extension of the ABI (exported by the same library)
+FIT_ABI_SYMBOLS = ("mrl_ggx_grad_batch",)
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -264,6 +266,7 @@ def load_library(path: Optional[str] = None):
         getattr(L, symbol).argtypes = [vp] + [fp] * len(ins) + [_SCALARS.get(name, vp) for name in middle] + [fp] * len(outs)
     L.mrl_partition_by_material.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
+    L.mrl_ggx_grad_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int32, C.c_size_t, vp, vp]
     L.mrl_generate_pairs.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, fp, fp, fp]
     L.mrl_generate_materials.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, vp]
     L.mrl_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -756,6 +759,36 @@ class MerlHip:
         self._check(self._lib.mrl_table_grad_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
                                                    _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), material, n, ptr), "mrl_table_grad_batch")
         return out
+
+    def ggx_grad(self, wi, wo, grad_rgb, material: int, curvature=None, normal: bool = False, out=None):
+        """The parameter gradient of eval on a GGX material (mrl_ggx_grad_batch), parameters in the order (alpha, eta[3], k[3]):
+        grad [7] += sum grad_rgb . J, and with normal=True also normal [7, 7] += sum curvature . J J^T (curvature None = 1).  f64;
+        numpy in -> numpy out, device tensors in -> device tensors out.  out= (grad, or (grad, normal)) is accumulated into; a
+        fresh result starts from zeros.  Returns grad, or (grad, normal)."""
+        n = int(wi.shape[0]); self._prep(wi)
+        outs = () if out is None else ((out,) if not normal else tuple(out))
+        if out is not None and len(outs) != (2 if normal else 1):
+            raise ValueError("out: need grad, or (grad, normal) with normal=True")
+        shapes = ((7,), (7, 7))[:2 if normal else 1]
+        if _is_tensor(wi):
+            import torch
+            if out is None:
+                outs = tuple(torch.zeros(s, dtype=torch.float64, device=wi.device) for s in shapes)
+            for o, s in zip(outs, shapes):
+                if not _is_tensor(o) or o.dtype != torch.float64 or not o.is_contiguous() or tuple(o.shape) != s:
+                    raise ValueError(f"out: need a contiguous torch.float64 tensor of shape {s}")
+            ptrs = [o.data_ptr() for o in outs]
+        else:
+            if out is None:
+                outs = tuple(np.zeros(s, dtype=np.float64) for s in shapes)
+            for o, s in zip(outs, shapes):
+                if not isinstance(o, np.ndarray) or o.dtype != np.float64 or not o.flags["C_CONTIGUOUS"] or o.shape != s:
+                    raise ValueError(f"out: need a C-contiguous numpy float64 array of shape {s}")
+            ptrs = [o.ctypes.data for o in outs]
+        self._check(self._lib.mrl_ggx_grad_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                                 _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(curvature, np.float32, 3, n, "curvature"),
+                                                 material, n, ptrs[0], ptrs[1] if normal else None), "mrl_ggx_grad_batch")
+        return outs if normal else outs[0]
 
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
