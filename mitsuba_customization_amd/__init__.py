@@ -7,5 +7,7 @@ Layout:
   host.py    ctypes host over the C ABI (tests, bench, sharding plumbing)
   shard.py   index-tile sharding + result gather over torch.distributed (RCCL on the GPU box)
   synth.py   synthetic MERL-layout tables and .binary file helpers
+  fit.py     fitting tables and GGX conductors to measurements over the gradients in the material
+  diff.py    eval of GGX conductors as a differentiable torch operation over the gradient in the directions
 """
 __all__ = ["host", "synth", "build"]

@@ -8,6 +8,7 @@
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
 //   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
+//   merl_ggx_dir_grad.hip  the direction gradient of eval on GGX conductors (mrl_ggx_grad_dir_batch / _queue): streaming kernel + calls
 #pragma once
 #include "../../include/merl_hip.h"
 

@@ -15,6 +15,7 @@ struct GgxConsts {                 // per material, computed once per launch (SG
     double alpha, inv_alpha2, inv_pi_alpha2;
     double eta2_k2[3];             // eta^2 - k^2
     double four_k2_eta2[3];        // 4 k^2 eta^2
+    GgxConsts() = default;         // filled in by ggx_consts_exact
     MRL_HD explicit GgxConsts(const MaterialDev &m)
     {
         alpha = m.alpha;
@@ -179,6 +180,143 @@ MRL_HD GgxJacobian ggx_eval_jacobian(const GgxConsts &g, const double eta[3], co
         j.d_k[ch] = k[ch] == 0.0 ? 0.0 : model * (2.0 * k[ch] * __builtin_fma(4.0 * e2, fQ, -fE));
     }
     return j;
+}
+
+// ---- the direction gradient of eval (merl_ggx_dir_grad.hip) ----
+// eval_c = F_c(c) M with M = D(m) G1(a) G1(b) / (4 a_z), a = wi / |wi|, b = wo / |wo|, h = a + b, m = h / |h|, c = a . m.  Only two
+// scalars depend on the channel, A = M sum g_c F_c and B = M sum g_c dF_c/dc; the vectors are channel-free:
+//     d/da = A (dlnD/dm_z (e_z - m m_z) / |h| + (dlnG1/da_z - 1/a_z) e_z) + B (m + (a - c m) / |h|)
+//     d/db = A (dlnD/dm_z (e_z - m m_z) / |h| +  dlnG1/db_z          e_z) + B      (a - c m) / |h|
+// (m = h / |h| pulls a vector v back to (v - m (m . v)) / |h|), and wi's gradient is (d/da - a (a . d/da)) / |wi|, likewise wo's.
+// On unit vectors D depends on m_z alone and G1(v) on v_z alone, and both enter through LOG-derivatives, as the alpha-derivatives
+// above do: nothing is divided by a D or G1 that vanishes.  Contraction is off and every fused multiply-add is spelt out: the
+// single-material and the material-per-lane kernel, with and without a queue, must round alike.
+
+// the constants of a material from its parameters, rounded the same way wherever this is inlined (the constructor above leaves
+// its contraction to the compiler)
+MRL_HD GgxConsts ggx_consts_exact(double alpha, const double eta[3], const double k[3])
+{
+#pragma clang fp contract(off)
+    GgxConsts g;
+    g.alpha = alpha;
+    g.inv_alpha2 = rcp_nr(alpha * alpha);
+    g.inv_pi_alpha2 = g.inv_alpha2 * 0.31830988618379067154;
+    for (int c = 0; c < 3; ++c) {
+        const double e2 = eta[c] * eta[c], k2 = k[c] * k[c];
+        g.eta2_k2[c] = e2 - k2;
+        g.four_k2_eta2[c] = 4.0 * k2 * e2;
+    }
+    return g;
+}
+
+// D as ggx_D_dlog returns it, and d ln D / d m_z on the unit sphere: root = s / a^2 + m_z^2 with s = 1 - m_z^2 gives
+// d root / d m_z = 2 m_z (1 - 1 / a^2) and ln D = -2 ln root + const
+MRL_HD double ggx_D_dz(const GgxConsts &g, const Vec3 &m, double &dlog)
+{
+#pragma clang fp contract(off)
+    const double s_a2 = __builtin_fma(m.x, m.x, m.y * m.y) * g.inv_alpha2, c2 = m.z * m.z;
+    const double inv = rcp_nr(__builtin_fmax(s_a2 + c2, kTiny));
+    const double r = g.inv_pi_alpha2 * (inv * inv);
+    dlog = 4.0 * (g.inv_alpha2 - 1.0) * (m.z * inv);
+    return (m.z <= 0.0 || r * m.z < 1e-20) ? 0.0 : r;
+}
+
+// G1 as ggx_G1_dlog returns it, 1 / v_z, and d ln G1 / d v_z on the unit sphere: with q = sqrt(v_z^2 + a^2 (1 - v_z^2)),
+// 1 / v_z - (1 + dq/dv_z) / (v_z + q) = a^2 / (v_z q (v_z + q)).  The exact-normal select (G1 = 1) has derivative 0.
+MRL_HD double ggx_G1_dz(const GgxConsts &g, const Vec3 &v, const Vec3 &m, double &dlog, double &inv_vz)
+{
+#pragma clang fp contract(off)
+    const double vm = __builtin_fma(v.x, m.x, __builtin_fma(v.y, m.y, v.z * m.z));
+    const double vz2 = v.z * v.z;
+    const double s2 = 1.0 - vz2;
+    const double az = __builtin_fabs(v.z);
+    double q, rq;
+    sqrt_rsqrt(__builtin_fma(g.alpha * g.alpha, s2, vz2), q, rq);
+    const double inv = rcp_nr(__builtin_fmax(az + q, kTiny));
+    inv_vz = rcp_nr(v.z);
+    const bool flat = s2 <= 0.0;
+    dlog = flat ? 0.0 : (g.alpha * g.alpha) * (rq * inv) * inv_vz;
+    const double res = flat ? 1.0 : 2.0 * az * inv;
+    return vm * v.z <= 0.0 ? 0.0 : res;
+}
+
+// F as fresnel_conductor_d returns it, and dF/dc from the same square roots and reciprocal.  With s2 = 1 - c^2, t1 = E - s2,
+// A = sqrt(t1^2 + Q), a = sqrt((A + t1) / 2):  dt1 = 2c, dA = 2c t1 / A, da = (dA + dt1) / (4a) = c a / A;
+// dT1 = dA + 2c, dT2 = 2 (a + c da), dT3 = c^2 dA + 2c (A - 2 s2), dT4 = s2 dT2 - 2c T2; dRs and dP as in fresnel_conductor_d.
+MRL_HD double fresnel_conductor_dc(const GgxConsts &g, int ch, double c, double &dc)
+{
+#pragma clang fp contract(off)
+    const double c2 = c * c, s2 = 1.0 - c2, s4 = s2 * s2;
+    const double t1 = g.eta2_k2[ch] - s2;
+    double A, rA, a, ra;
+    sqrt_rsqrt(__builtin_fma(t1, t1, g.four_k2_eta2[ch]), A, rA);
+    sqrt_rsqrt(0.5 * (A + t1), a, ra);
+    const double term1 = A + c2, term2 = 2.0 * a * c;
+    const double term3 = __builtin_fma(A, c2, s4), term4 = term2 * s2;
+    const double d12 = term1 + term2, d34 = term3 + term4;
+    const double inv = rcp_nr(d12 * d34);
+    const double inv12 = d34 * inv, inv34 = d12 * inv;
+    const double rs = (term1 - term2) * inv12, p1 = 1.0 + (term3 - term4) * inv34;
+    const double k12 = 2.0 * (inv12 * inv12) * p1, k34 = 2.0 * (inv34 * inv34) * rs;
+    const double two_c = 2.0 * c;
+    const double dA = two_c * (t1 * rA);
+    const double dT1 = dA + two_c;
+    const double dT2 = 2.0 * (a * __builtin_fma(c2, rA, 1.0));
+    const double dT3 = __builtin_fma(c2, dA, two_c * (A - 2.0 * s2));
+    const double dT4 = __builtin_fma(s2, dT2, -(two_c * term2));
+    dc = 0.5 * __builtin_fma(k12, __builtin_fma(term2, dT1, -(term1 * dT2)), k34 * __builtin_fma(term4, dT3, -(term3 * dT4)));
+    return 0.5 * (rs * p1);
+}
+
+// sum_c g_c d eval_c / d wi and the same in wo, for one pair of raw Float directions (the normalisation is part of the function: each
+// gradient is orthogonal to its direction and scales with 1 / |w|).  A unit that eval masks, or for which one of eval's D / G1
+// selects returns 0, gets +0 in both — by selects at the end: its values are garbage and its g may be NaN.
+struct GgxDirGrad { float wi[3], wo[3]; };
+MRL_HD GgxDirGrad ggx_eval_dir_grad(const GgxConsts &g, float wix, float wiy, float wiz, float wox, float woy, float woz, const float g32[3])
+{
+#pragma clang fp contract(off)
+    const Dir di = dir_f32(wix, wiy, wiz), dout = dir_f32(wox, woy, woz);
+    const Vec3 a = unit(di), b = unit(dout);
+    const double hx = a.x + b.x, hy = a.y + b.y, hz = a.z + b.z;
+    double L, rL;
+    sqrt_rsqrt(__builtin_fma(hx, hx, __builtin_fma(hy, hy, hz * hz)), L, rL);
+    const Vec3 m = { hx * rL, hy * rL, hz * rL };
+    double kD, kGa, kGb, inv_az, inv_bz;
+    const double D = ggx_D_dz(g, m, kD);
+    const double G1a = ggx_G1_dz(g, a, m, kGa, inv_az);
+    const double G1b = ggx_G1_dz(g, b, m, kGb, inv_bz);
+    const double M = D * G1a * (0.25 * inv_az) * G1b;
+    const double c = __builtin_fma(a.x, m.x, __builtin_fma(a.y, m.y, a.z * m.z));
+    double sF = 0.0, sdF = 0.0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        double dF;
+        const double F = fresnel_conductor_dc(g, ch, c, dF);
+        const double gc = (double)g32[ch];
+        sF = __builtin_fma(gc, F, sF);
+        sdF = __builtin_fma(gc, dF, sdF);
+    }
+    const double A = M * sF, B = M * sdF;
+    // what both sides share: T = (A dlnD/dm_z / |h|) (e_z - m m_z) + (B / |h|) (a - c m); the z of e_z - m m_z is m_x^2 + m_y^2
+    const double p = A * kD * rL, q = B * rL;
+    const double tx = __builtin_fma(p, -(m.x * m.z), q * __builtin_fma(-c, m.x, a.x));
+    const double ty = __builtin_fma(p, -(m.y * m.z), q * __builtin_fma(-c, m.y, a.y));
+    const double tz = __builtin_fma(p, __builtin_fma(m.x, m.x, m.y * m.y), q * __builtin_fma(-c, m.z, a.z));
+    const double vax = __builtin_fma(B, m.x, tx), vay = __builtin_fma(B, m.y, ty);
+    const double vaz = __builtin_fma(B, m.z, __builtin_fma(A, kGa - inv_az, tz));
+    const double vbz = __builtin_fma(A, kGb, tz);
+    const double da = __builtin_fma(a.x, vax, __builtin_fma(a.y, vay, a.z * vaz));
+    const double db = __builtin_fma(b.x, tx, __builtin_fma(b.y, ty, b.z * vbz));
+    const float poison = cos_or_nan32((wix + wiy + wiz), wox, woy, woz, true);
+    const bool live = (wiz > 0.0f) && (woz > 0.0f) && (poison == poison) && D != 0.0 && G1a != 0.0 && G1b != 0.0;
+    GgxDirGrad r;
+    r.wi[0] = live ? (float)(__builtin_fma(-a.x, da, vax) * di.rs) : 0.0f;
+    r.wi[1] = live ? (float)(__builtin_fma(-a.y, da, vay) * di.rs) : 0.0f;
+    r.wi[2] = live ? (float)(__builtin_fma(-a.z, da, vaz) * di.rs) : 0.0f;
+    r.wo[0] = live ? (float)(__builtin_fma(-b.x, db, tx) * dout.rs) : 0.0f;
+    r.wo[1] = live ? (float)(__builtin_fma(-b.y, db, ty) * dout.rs) : 0.0f;
+    r.wo[2] = live ? (float)(__builtin_fma(-b.z, db, vbz) * dout.rs) : 0.0f;
+    return r;
 }
 
 // sin / cos of 2 pi u for u in [0,1): only the normal-incidence branch of the sampler needs it.  That branch is taken

@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
 )
 # every symbol include/merl_hip_fit.h declares, the fitting extension of the ABI (exported by the same library)
 FIT_ABI_SYMBOLS = ("mrl_ggx_grad_batch",)
+# every symbol include/merl_hip_diff.h declares, the differentiation extension of the ABI (exported by the same library)
+DIFF_ABI_SYMBOLS = ("mrl_ggx_grad_dir_batch", "mrl_ggx_grad_dir_queue")
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -267,6 +269,8 @@ def load_library(path: Optional[str] = None):
     L.mrl_partition_by_material.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
     L.mrl_ggx_grad_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int32, C.c_size_t, vp, vp]
+    L.mrl_ggx_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
+    L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
     L.mrl_generate_pairs.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, fp, fp, fp]
     L.mrl_generate_materials.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, vp]
     L.mrl_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -790,6 +794,35 @@ class MerlHip:
                                                  material, n, ptrs[0], ptrs[1] if normal else None), "mrl_ggx_grad_batch")
         return outs if normal else outs[0]
 
+    def _grad_dir_outputs(self, wi, want, out, alloc):
+        """(grad_wi or None, grad_wo or None) for `want`, a subset of ("wi", "wo") in that order: taken from out= (one array, or a
+        tuple in want's order) or allocated."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("wi", "wo") for w in want) or len(set(want)) != len(want) or want == ("wo", "wi"):
+            raise ValueError('want: "wi", "wo" or ("wi", "wo")')
+        n = int(wi.shape[0])
+        if out is None:
+            outs = tuple(alloc(wi, (n, 3)) for _ in want)
+        else:
+            outs = (out,) if len(want) == 1 and not isinstance(out, (tuple, list)) else tuple(out)
+            if len(outs) != len(want):
+                raise ValueError(f"out: {len(want)} arrays wanted, got {len(outs)}")
+        by_name = dict(zip(want, outs))
+        return by_name.get("wi"), by_name.get("wo"), outs
+
+    def ggx_grad_dir(self, wi, wo, grad_rgb, mat=None, material: int = 0, want=("wi", "wo"), out=None):
+        """The direction gradient of eval on GGX materials (mrl_ggx_grad_dir_batch): per unit grad_wi = sum_c grad_rgb_c d eval_c / d wi
+        and the same in wo, [n, 3] f32, overwritten; a dead unit, and with mat= a unit whose id names no live GGX material, gets
+        zeros.  want: which of the two to compute.  numpy in -> numpy out, device tensors in -> device tensors out.  Returns the
+        gradient wanted, or (grad_wi, grad_wo)."""
+        n = int(wi.shape[0]); self._prep(wi)
+        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._empty)
+        self._check(self._lib.mrl_ggx_grad_dir_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                                     _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material, n,
+                                                     _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
+                    "mrl_ggx_grad_dir_batch")
+        return outs[0] if len(outs) == 1 else outs
+
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
 
@@ -838,6 +871,18 @@ class MerlHip:
     def eval_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
         """eval() of the slots queue[0 .. min(count, capacity)); other slots of `out` stay as they are."""
         return _stream_call(self, "queue", "eval", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
+
+    def ggx_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
+        """ggx_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_grad_dir_queue); other slots of `out` stay as they
+        are (outputs allocated here start from zeros)."""
+        n = int(wi.shape[0])
+        q, q_count, cap = self._queue(wi, queue, count, capacity)
+        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._zeros)
+        self._check(self._lib.mrl_ggx_grad_dir_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                                     _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material,
+                                                     q, q_count, cap, _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
+                    "mrl_ggx_grad_dir_queue")
+        return outs[0] if len(outs) == 1 else outs
 
     def pdf_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
         return _stream_call(self, "queue", "pdf", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
