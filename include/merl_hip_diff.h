@@ -1,6 +1,7 @@
 /* merl_hip_diff.h — the differentiation extension of the C ABI of libmerl_hip.so: the gradient of eval in the directions.
  * It includes merl_hip.h (contexts, materials, status codes, mrl_eval_batch, mrl_eval_queue) and adds to it; the library exports
- * both sets.  The gradients in the material live in merl_hip_fit.h (mrl_ggx_grad_batch) and merl_hip.h (mrl_table_grad_batch).
+ * both sets.  The gradients in the material live in merl_hip_fit.h (mrl_ggx_grad_batch) and merl_hip.h (mrl_table_grad_batch); the
+ * direction gradient on table materials lives in merl_hip_diff_table.h.
  * Calls added here are listed in host.DIFF_ABI_SYMBOLS and checked against this header by tests/test_ggx_dir_grad_cpu.py. */
 #ifndef MERL_HIP_DIFF_H
 #define MERL_HIP_DIFF_H
@@ -36,8 +37,9 @@ extern "C" {
  * DETERMINISM (a contract of these calls): a unit's output bits depend on its own inputs and its material's parameters alone —
  * the whole-array, material-id, queue and host-array forms return identical bits for the same unit, whatever n, the grid or the
  * unit's position, and grad_wi has the same bits with and without grad_wo.
- * Not offered: table and RGL materials, n-channel tables, device groups (mrl_group_*), the one-unit paths, second derivatives,
- * gradients of pdf and sample. */
+ * Not offered here: RGB table materials have the same pair of calls in merl_hip_diff_table.h (mrl_table_grad_dir_batch / _queue).
+ * Not offered: RGL materials, n-channel tables, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf
+ * and sample. */
 int mrl_ggx_grad_dir_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                            const int32_t *mat, int32_t single_id, size_t n,
                            float *grad_wi, float *grad_wo);

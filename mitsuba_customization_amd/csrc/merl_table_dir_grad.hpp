@@ -1,0 +1,219 @@
+// merl_table_dir_grad.hpp — the per-lane gradient of eval in the directions on an RGB table material (include/merl_hip_diff_table.h,
+// DESIGN.md §5j): the function k_table_grad_dir runs, __host__ __device__ and free of HIP calls so that a host harness can run it.
+//
+// E_c(wi, wo) = T_c(x(a, b)) kappa with a = wi / |wi|, b = wo / |wo|, x the table coordinates of merl_table_fast.hpp, T_c the exact
+// trilinear interpolant of the stored Float texels in the cell eval selects, kappa the Float wo.z (or 1).  Reverse mode, for the
+// cotangent g of the three channels:
+//   1. per channel the cell's texels are first taken relative to corner 0, u_k[c] = f[k][c] - f[0][c]: differences of Floats, exact
+//      in f64 (to 2^-53 of themselves when the exponents lie more than 29 apart).  These are contracted with g corner by corner,
+//      t_k = sum_c g_c u_k[c], t_0 = 0.  V = sum_c g_c T_c is sum_c g_c f[0][c] plus the trilinear form of the t_k, and
+//      D_axis = sum_c g_c dT_c / df_axis the bilinear form of the differences of the t_k along the axis, all with f64 weights: nothing
+//      of the Float corner weights or the packed Float blend of eval enters.  A t_k carries three f64 roundings of
+//      sum_c |g_c| |f[k][c] - f[0][c]|, so the error of a D_axis is 2^-51 of sum_c |g_c| times the VARIATION of channel c inside the
+//      cell — never of a channel's magnitude: a large flat channel next to a small smooth one contributes exact zeros.  Equal texels
+//      give exactly 0.  (Contracting the raw texels first is no cheaper and wrong by 2^-53 of the largest |g_c f_c|; taking
+//      all twelve edge differences per channel first is the same as this to 1e-15 of the cell's variation and compiles to 166 VGPRs
+//      against 136 to 142: still three waves per SIMD, but under that bound of 168 the material-id kernels spill 12 B per lane);
+//   2. the three D_axis are pulled back through the coordinate map onto the unit vectors a and b.  atan2(y, x) has the derivative
+//      (x dy - y dx) / (x^2 + y^2), d xh / d theta_h = k_th / (2 xh): no polynomial, no libm, reciprocals and square roots from the
+//      library's seeds + Newton steps;
+//   3. through the two normalisations, (v - w (w . v) / |w|^2) / |w|, and the cosine: grad_wo.z += V.
+// A clamped fraction has derivative 0 while its clamp is active; the padded upper end has it through its equal texels.  Where a
+// coordinate map has no derivative (h == n, retro-reflection, px == py == 0; a direction at the normal in the standard forms) that
+// coordinate's term is dropped by a select BEFORE any product, so no 0 * inf is formed.  A nearest lookup (MRL_OPT_LOOKUP = 0) is
+// the same code with the nearest cell, zero fractions and zero masks: V is then the texel itself and every D_axis is 0.
+// Contraction is off and the FMAs are spelt out: a unit's bits do not depend on the kernel the function is inlined into.
+#pragma once
+#include "merl_table_fast.hpp"
+
+namespace mrl {
+namespace fast {
+
+struct TableDirGrad { float wi[3], wo[3]; };
+
+// below this a singular measure (rho^2, |e|^2, px^2 + py^2, ...) counts as zero: its reciprocal stays finite
+constexpr double kSingular = 1e-280;
+
+// the 24 floats of the cell (h0, d0, p0): corner-major RGB, corner k = 4 a + 2 b + c along (axis 0, axis 1, azimuth) — all loads are
+// issued before any use
+template <int LAYOUT>
+MRL_HD void load_cell(const MaterialDev &m, int h0, int d0, int p0, float f[24])
+{
+    if constexpr (LAYOUT == LAYOUT_BRICK) {
+        const float4 *q = m.texels + (((size_t)h0 * m.n_td + d0) * m.n_pd + p0) * 8;
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+        f[0] = q0.x; f[1] = q0.y; f[2] = q0.z; f[3] = q0.w; f[4] = q1.x; f[5] = q1.y; f[6] = q1.z; f[7] = q1.w;
+        f[8] = q2.x; f[9] = q2.y; f[10] = q2.z; f[11] = q2.w; f[12] = q3.x; f[13] = q3.y; f[14] = q3.z; f[15] = q3.w;
+        f[16] = q4.x; f[17] = q4.y; f[18] = q4.z; f[19] = q4.w; f[20] = q5.x; f[21] = q5.y; f[22] = q5.z; f[23] = q5.w;
+    } else {
+        const float4 *b = m.texels + ((size_t)h0 * m.row_th + (size_t)d0 * m.row_td + p0);
+        const float4 t0 = b[0], t1 = b[1], t2 = b[m.row_td], t3 = b[m.row_td + 1];
+        const float4 t4 = b[m.row_th], t5 = b[m.row_th + 1], t6 = b[m.row_th + m.row_td], t7 = b[m.row_th + m.row_td + 1];
+        f[0] = t0.x; f[1] = t0.y; f[2] = t0.z; f[3] = t1.x; f[4] = t1.y; f[5] = t1.z; f[6] = t2.x; f[7] = t2.y; f[8] = t2.z;
+        f[9] = t3.x; f[10] = t3.y; f[11] = t3.z; f[12] = t4.x; f[13] = t4.y; f[14] = t4.z; f[15] = t5.x; f[16] = t5.y; f[17] = t5.z;
+        f[18] = t6.x; f[19] = t6.y; f[20] = t6.z; f[21] = t7.x; f[22] = t7.y; f[23] = t7.z;
+    }
+}
+
+// (1 - t) u + t v
+MRL_HD double lerp_fma(double s, double t, double u, double v)
+{
+#pragma clang fp contract(off)
+    return __builtin_fma(t, v, s * u);
+}
+
+// what the pull-backs return: the cotangents of the unit vectors a and b
+struct UnitAdjoint { double ax, ay, az, bx, by, bz; };
+
+// half / difference angles: x = (sqrt(theta_h k_th), theta_d k_td, phi_d k_pd) of s = a + b, e = a - b (coords() above).
+// Xh, Xd, Xp: the cotangents of the three coordinates; xh: the first coordinate itself
+MRL_HD UnitAdjoint pull_half_diff(const Vec3 &a, const Vec3 &b, double k_th, double k_td, double k_pd, double xh, double Xh, double Xd, double Xp)
+{
+#pragma clang fp contract(off)
+    const double sx = a.x + b.x, sy = a.y + b.y, sz = a.z + b.z;
+    const double ex = a.x - b.x, ey = a.y - b.y, ez = a.z - b.z;
+    const double rho2 = __builtin_fma(sx, sx, sy * sy);
+    const double s2 = __builtin_fma(sz, sz, rho2);
+    const double e2 = __builtin_fma(ex, ex, __builtin_fma(ey, ey, ez * ez));
+    const bool ok_h = rho2 > kSingular, ok_e = e2 > kSingular;
+    const double irho = rsqrt_pos(ok_h ? rho2 : 1.0), rho = rho2 * irho;
+    const double ins = rsqrt_pos(s2), ns = s2 * ins;                // |s| > 0 on every live unit (s_z > 0)
+    const double ine = rsqrt_pos(ok_e ? e2 : 1.0), ne = e2 * ine;
+    // theta_h = atan2(rho, s_z), xh = sqrt(theta_h k_th): d xh / d theta_h = k_th / (2 xh)
+    const double th_bar = ok_h ? Xh * (0.5 * k_th) * rcp_nr(xh) : 0.0;
+    const double c_h = th_bar * (ins * ins);
+    const double hz = c_h * sz * irho;
+    double s_x = hz * sx, s_y = hz * sy, s_z = -(c_h * rho);
+    // theta_d = atan2(|e|, |s|)
+    const double q = ok_e ? Xd * k_td * rcp_nr(e2 + s2) : 0.0;
+    double c_s = -(q * ne * ins);                                   // times s
+    const double c_e = q * ns * ine;                                // times e
+    double e_x = c_e * ex, e_y = c_e * ey, e_z = c_e * ez;
+    // phi_d = atan2(py, px) mod pi, py = e_y s_x - e_x s_y, px = -e_z |s|
+    const double py = __builtin_fma(ey, sx, -(ex * sy)), px = -ez * ns;
+    const double pp = __builtin_fma(px, px, py * py);
+    const bool ok_p = ok_h && pp > kSingular;
+    const double r = ok_p ? Xp * k_pd * rcp_nr(ok_p ? pp : 1.0) : 0.0;
+    const double py_bar = r * px, px_bar = -(r * py);
+    s_x = __builtin_fma(py_bar, ey, s_x); s_y = __builtin_fma(-py_bar, ex, s_y);
+    e_y = __builtin_fma(py_bar, sx, e_y); e_x = __builtin_fma(-py_bar, sy, e_x);
+    e_z = __builtin_fma(-px_bar, ns, e_z);
+    c_s = __builtin_fma(-px_bar, ez * ins, c_s);
+    s_x = __builtin_fma(c_s, sx, s_x); s_y = __builtin_fma(c_s, sy, s_y); s_z = __builtin_fma(c_s, sz, s_z);
+    return { s_x + e_x, s_y + e_y, s_z + e_z, s_x - e_x, s_y - e_y, s_z - e_z };
+}
+
+// the standard forms: x = (theta_i k_0, theta_o k_1, dphi k_2), theta = atan2(|v_xy|, v_z), dphi = atan2(cr, dt) — its magnitude in
+// the mirrored form (sign(cr) is the derivative of the fold), itself in the full one (coords_standard() above)
+MRL_HD UnitAdjoint pull_standard(const Vec3 &a, const Vec3 &b, bool full, double k_0, double k_1, double k_2, double Xh, double Xd, double Xp)
+{
+#pragma clang fp contract(off)
+    const double ra2 = __builtin_fma(a.x, a.x, a.y * a.y), rb2 = __builtin_fma(b.x, b.x, b.y * b.y);
+    const bool ok_a = ra2 > kSingular, ok_b = rb2 > kSingular;
+    const double ira = rsqrt_pos(ok_a ? ra2 : 1.0), irb = rsqrt_pos(ok_b ? rb2 : 1.0);
+    const double c_a = ok_a ? Xh * k_0 * rcp_nr(__builtin_fma(a.z, a.z, ra2)) : 0.0;
+    const double c_b = ok_b ? Xd * k_1 * rcp_nr(__builtin_fma(b.z, b.z, rb2)) : 0.0;
+    const double az = c_a * a.z * ira, bz = c_b * b.z * irb;
+    UnitAdjoint u = { az * a.x, az * a.y, -(c_a * (ra2 * ira)), bz * b.x, bz * b.y, -(c_b * (rb2 * irb)) };
+    const double cr = __builtin_fma(a.x, b.y, -(a.y * b.x)), dt = __builtin_fma(a.x, b.x, a.y * b.y);
+    const double cc = __builtin_fma(cr, cr, dt * dt);
+    const bool ok_c = cc > kSingular;
+    const double xp = (!full && cr < 0.0) ? -Xp : Xp;
+    const double r = ok_c ? xp * k_2 * rcp_nr(ok_c ? cc : 1.0) : 0.0;
+    const double cr_bar = r * dt, dt_bar = -(r * cr);
+    u.ax = __builtin_fma(cr_bar, b.y, __builtin_fma(dt_bar, b.x, u.ax));
+    u.ay = __builtin_fma(-cr_bar, b.x, __builtin_fma(dt_bar, b.y, u.ay));
+    u.bx = __builtin_fma(-cr_bar, a.y, __builtin_fma(dt_bar, a.x, u.bx));
+    u.by = __builtin_fma(cr_bar, a.x, __builtin_fma(dt_bar, a.y, u.by));
+    return u;
+}
+
+// a cotangent of the unit vector u = w / |w| taken back to w: (v - u (u . v)) / |w|, times the factor k, as Float
+MRL_HD void through_normalisation(const Vec3 &u, double rs, double vx, double vy, double vz, double k, double out[3])
+{
+#pragma clang fp contract(off)
+    const double d = __builtin_fma(u.x, vx, __builtin_fma(u.y, vy, u.z * vz));
+    const double s = rs * k;
+    out[0] = __builtin_fma(-u.x, d, vx) * s; out[1] = __builtin_fma(-u.y, d, vy) * s; out[2] = __builtin_fma(-u.z, d, vz) * s;
+}
+
+// into the Float range; a NaN (a live unit whose cotangent overflows: inf - inf in the projections) becomes 0, not a number
+MRL_HD float finite_f32(double x)
+{
+    const double c = __builtin_fmin(__builtin_fmax(x, -3.4028234663852886e38), 3.4028234663852886e38);
+    return x == x ? (float)c : 0.0f;
+}
+
+// grad_wi = sum_c g_c dE_c / d wi and grad_wo of ONE unit on the RGB table m (kind MERL / TABLE, its texels in layout LAYOUT) under the
+// options o (lookup, node, cosine; negative is a property of the stored texels here).  Dead units — eval's: wi.z <= 0, wo.z <= 0, a
+// NaN / inf component — get +0.0f from a select at the very end, whatever g holds.
+template <int LAYOUT>
+MRL_HD TableDirGrad table_eval_dir_grad(const MaterialDev &m, const Options &o, float wix, float wiy, float wiz, float wox, float woy, float woz,
+                                        const float g32[3])
+{
+#pragma clang fp contract(off)
+    const TableMaps maps(m);
+    const Dir in_dir = dir_f32(wix, wiy, wiz), out_dir = dir_f32(wox, woy, woz);
+    const Vec3 a = unit(in_dir), b = unit(out_dir);
+    const Coords c = maps(normalize_f32(wix, wiy, wiz), out_dir);           // eval's own coordinates: they select the cell
+    const bool trilinear = o.lookup != 0, periodic = param_phi_periodic(m.param);
+    const double shift = (trilinear && o.node) ? 0.5 : 0.0;
+    const double xh = c.xh - shift, xd = c.xd - shift, xp = c.xp - shift;
+    int h0, d0, p0;
+    double fh, fd, fp;
+    split_clamped(xh, m.n_th, h0, fh);
+    split_clamped(xd, m.n_td, d0, fd);
+    split_phi(periodic, xp, m.n_pd, p0, fp);
+    // a nearest lookup: lookup_nearest_t's cell, no fractions
+    h0 = trilinear ? h0 : trunc_i(c.xh); d0 = trilinear ? d0 : trunc_i(c.xd); p0 = trilinear ? p0 : trunc_i(c.xp);
+    fh = trilinear ? fh : 0.0; fd = trilinear ? fd : 0.0; fp = trilinear ? fp : 0.0;
+    // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table
+    h0 = clampi(h0, 0, m.n_th - 1); d0 = clampi(d0, 0, m.n_td - 1); p0 = clampi(p0, 0, m.n_pd - 1);
+    float f[24];
+    load_cell<LAYOUT>(m, h0, d0, p0, f);
+
+    // 1. per channel the seven exact differences to corner 0, u_k[c] = f[k][c] - f[0][c], contracted with g: t_k = sum_c g_c u_k[c] (t_0 = 0).
+    //    V is sum_c g_c f[0][c] plus the trilinear form of the t_k, the three D_axis the bilinear forms of their differences
+    const double g[3] = { (double)g32[0], (double)g32[1], (double)g32[2] };
+    const double b0 = (double)f[0], b1 = (double)f[1], b2 = (double)f[2];
+    double t[8];
+    t[0] = 0.0;
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        t[k] = __builtin_fma(g[2], (double)f[3 * k + 2] - b2, __builtin_fma(g[1], (double)f[3 * k + 1] - b1, g[0] * ((double)f[3 * k] - b0)));
+    const double gh = 1.0 - fh, gd = 1.0 - fd, gp = 1.0 - fp;
+    const double V = __builtin_fma(g[2], b2, __builtin_fma(g[1], b1, g[0] * b0)) +
+                     lerp_fma(gh, fh, lerp_fma(gd, fd, fp * t[1], lerp_fma(gp, fp, t[2], t[3])),
+                              lerp_fma(gd, fd, lerp_fma(gp, fp, t[4], t[5]), lerp_fma(gp, fp, t[6], t[7])));
+    // corners (k, k + 1) along the azimuth, (k, k + 2) along axis 1, (k, k + 4) along axis 0
+    const double Dp = lerp_fma(gh, fh, lerp_fma(gd, fd, t[1], t[3] - t[2]), lerp_fma(gd, fd, t[5] - t[4], t[7] - t[6]));
+    const double Dd = lerp_fma(gh, fh, lerp_fma(gp, fp, t[2], t[3] - t[1]), lerp_fma(gp, fp, t[6] - t[4], t[7] - t[5]));
+    const double Dh = lerp_fma(gd, fd, lerp_fma(gp, fp, t[4], t[5] - t[1]), lerp_fma(gp, fp, t[6] - t[2], t[7] - t[3]));
+    // df / dx is 1 inside the cell; 0 under an active lower clamp (the upper end has equal texels: its D is 0) and for nearest
+    const double Xh = (trilinear && xh >= 0.0) ? Dh : 0.0;
+    const double Xd = (trilinear && xd >= 0.0) ? Dd : 0.0;
+    const double Xp = (trilinear && (periodic || xp >= 0.0)) ? Dp : 0.0;
+
+    // 2. through the coordinate map (a wave-uniform branch for a single-material launch)
+    const UnitAdjoint u = m.param == PARAM_HALF_DIFF ? pull_half_diff(a, b, maps.k_th, maps.k_td, maps.k_pd, c.xh, Xh, Xd, Xp)
+                                                     : pull_standard(a, b, m.param == PARAM_STANDARD_FULL, maps.k_th, maps.k_td, maps.k_pd, Xh, Xd, Xp);
+
+    // 3. through the normalisations and the cosine factor: kappa is eval_tail's Float wo.z (or 1; NaN when an input is not finite)
+    const bool no_cosine = o.cosine != 0;
+    const float kappa = cos_or_nan32((wix + wiy + wiz), wox, woy, woz, no_cosine);
+    const bool live = (wiz > 0.0f) && (woz > 0.0f) && (kappa == kappa);
+    double gi[3], go[3];
+    through_normalisation(a, in_dir.rs, u.ax, u.ay, u.az, (double)kappa, gi);
+    through_normalisation(b, out_dir.rs, u.bx, u.by, u.bz, (double)kappa, go);
+    go[2] += no_cosine ? 0.0 : V;
+    TableDirGrad r;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        r.wi[k] = live ? finite_f32(gi[k]) : 0.0f;
+        r.wo[k] = live ? finite_f32(go[k]) : 0.0f;
+    }
+    return r;
+}
+
+} // namespace fast
+} // namespace mrl
