@@ -69,10 +69,10 @@ def fit(eval_fn, wi_w, wo_w, y=None, start=(0.0, 0.0), iters=8, dtype=torch.floa
         dr = torch.autograd.functional.jacobian(rotation, q.detach()).to(wi_w.device)        # [3, 3, 2]
         dwi, dwo = torch.einsum("uk,ikj->uij", wi_w, dr), torch.einsum("uk,ikj->uij", wo_w, dr)
         jac = []
-        for c in range(3):                                      # one-hot channel weights: the wrapper's backward, three times
+        for c in range(r.shape[1]):                             # one-hot channel weights: the wrapper's backward, once per channel
             ji, jo = torch.autograd.grad(rgb[:, c].sum(), (wi_l, wo_l), retain_graph=True)
             jac.append(torch.einsum("ui,uij->uj", ji.to(torch.float64), dwi) + torch.einsum("ui,uij->uj", jo.to(torch.float64), dwo))
-        jac = torch.stack(jac, 1)                               # [n, 3, 2]
+        jac = torch.stack(jac, 1)                               # [n, channels, 2]
         (r ** 2).sum().backward()                               # ... and once more, all the way to the angles: q.grad = 2 J^T r
         jtr = 0.5 * q.grad
         jtj = torch.einsum("uci,ucj->ij", jac, jac).cpu()

@@ -9,6 +9,8 @@
 //   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
 //   merl_ggx_dir_grad.hip  the direction gradient of eval on GGX conductors (mrl_ggx_grad_dir_batch / _queue): streaming kernel + calls
+//   merl_table_dir_grad.hip  the same on RGB tables (mrl_table_grad_dir_batch / _queue)
+//   merl_nch_dir_grad.hip  the same on n-channel tables (mrl_table_grad_dir_batch_nch / _queue_nch)
 #pragma once
 #include "../../include/merl_hip.h"
 

@@ -144,6 +144,95 @@ MRL_HD float finite_f32(double x)
     return x == x ? (float)c : 0.0f;
 }
 
+// table_eval_dir_grad below in three parts, so that the n-channel function (merl_nch_dir_grad.hpp) runs the second and the third on
+// its own t_k: the operations and their order are those of the one function this was.
+// Part 1, cell selection: the unit vectors, eval's own coordinates, the cell (h0, d0, p0) eval selects and its fractions
+struct DirCell {
+    Dir in_dir, out_dir;
+    Vec3 a, b;
+    double c_xh;                 // the unshifted first coordinate (the sqrt warp's derivative needs it)
+    bool mh, md, mp;             // df / dx is 1: trilinear, and no lower clamp active on the shifted coordinate (the azimuth: or periodic)
+    double fh, fd, fp;
+    double k_th, k_td, k_pd;
+    int h0, d0, p0;
+    bool trilinear, periodic;
+    float kappa;                 // eval_tail's Float wo.z (or 1; NaN when an input is not finite)
+    bool live;                   // not one of eval's dead units
+};
+
+MRL_HD DirCell dir_cell(const MaterialDev &m, const Options &o, float wix, float wiy, float wiz, float wox, float woy, float woz)
+{
+#pragma clang fp contract(off)
+    DirCell s;
+    const TableMaps maps(m);
+    s.in_dir = dir_f32(wix, wiy, wiz); s.out_dir = dir_f32(wox, woy, woz);
+    s.a = unit(s.in_dir); s.b = unit(s.out_dir);
+    const Coords c = maps(normalize_f32(wix, wiy, wiz), s.out_dir);         // eval's own coordinates: they select the cell
+    s.trilinear = o.lookup != 0; s.periodic = param_phi_periodic(m.param);
+    const double shift = (s.trilinear && o.node) ? 0.5 : 0.0;
+    s.c_xh = c.xh;
+    const double xh = c.xh - shift, xd = c.xd - shift, xp = c.xp - shift;
+    s.mh = s.trilinear && xh >= 0.0; s.md = s.trilinear && xd >= 0.0; s.mp = s.trilinear && (s.periodic || xp >= 0.0);
+    s.k_th = maps.k_th; s.k_td = maps.k_td; s.k_pd = maps.k_pd;
+    int h0, d0, p0;
+    double fh, fd, fp;
+    split_clamped(xh, m.n_th, h0, fh);
+    split_clamped(xd, m.n_td, d0, fd);
+    split_phi(s.periodic, xp, m.n_pd, p0, fp);
+    // a nearest lookup: lookup_nearest_t's cell, no fractions
+    h0 = s.trilinear ? h0 : trunc_i(c.xh); d0 = s.trilinear ? d0 : trunc_i(c.xd); p0 = s.trilinear ? p0 : trunc_i(c.xp);
+    s.fh = s.trilinear ? fh : 0.0; s.fd = s.trilinear ? fd : 0.0; s.fp = s.trilinear ? fp : 0.0;
+    // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table
+    s.h0 = clampi(h0, 0, m.n_th - 1); s.d0 = clampi(d0, 0, m.n_td - 1); s.p0 = clampi(p0, 0, m.n_pd - 1);
+    s.kappa = cos_or_nan32((wix + wiy + wiz), wox, woy, woz, o.cosine != 0);
+    s.live = (wiz > 0.0f) && (woz > 0.0f) && (s.kappa == s.kappa);
+    return s;
+}
+
+// Part 2, the forms of the t_k (t[0] == 0): V = base + the trilinear form, and the three bilinear forms of the differences along the
+// axes, masked: df / dx is 1 inside the cell; 0 under an active lower clamp (the upper end has equal texels: its D is 0) and for nearest
+struct DirForms { double V, Xh, Xd, Xp; };
+
+MRL_HD DirForms dir_forms(const DirCell &s, const double t[8], double base)
+{
+#pragma clang fp contract(off)
+    const double fh = s.fh, fd = s.fd, fp = s.fp;
+    const double gh = 1.0 - fh, gd = 1.0 - fd, gp = 1.0 - fp;
+    DirForms r;
+    r.V = base + lerp_fma(gh, fh, lerp_fma(gd, fd, fp * t[1], lerp_fma(gp, fp, t[2], t[3])),
+                          lerp_fma(gd, fd, lerp_fma(gp, fp, t[4], t[5]), lerp_fma(gp, fp, t[6], t[7])));
+    // corners (k, k + 1) along the azimuth, (k, k + 2) along axis 1, (k, k + 4) along axis 0
+    const double Dp = lerp_fma(gh, fh, lerp_fma(gd, fd, t[1], t[3] - t[2]), lerp_fma(gd, fd, t[5] - t[4], t[7] - t[6]));
+    const double Dd = lerp_fma(gh, fh, lerp_fma(gp, fp, t[2], t[3] - t[1]), lerp_fma(gp, fp, t[6] - t[4], t[7] - t[5]));
+    const double Dh = lerp_fma(gd, fd, lerp_fma(gp, fp, t[4], t[5] - t[1]), lerp_fma(gp, fp, t[6] - t[2], t[7] - t[3]));
+    r.Xh = s.mh ? Dh : 0.0;
+    r.Xd = s.md ? Dd : 0.0;
+    r.Xp = s.mp ? Dp : 0.0;
+    return r;
+}
+
+// Part 3, pull-back and tail: through the coordinate map (a wave-uniform branch for a single-material launch), the normalisations
+// and the cosine factor, and the dead-unit select
+MRL_HD TableDirGrad dir_tail(int param, const Options &o, const DirCell &s, const DirForms &F)
+{
+#pragma clang fp contract(off)
+    const UnitAdjoint u = param == PARAM_HALF_DIFF ? pull_half_diff(s.a, s.b, s.k_th, s.k_td, s.k_pd, s.c_xh, F.Xh, F.Xd, F.Xp)
+                                                   : pull_standard(s.a, s.b, param == PARAM_STANDARD_FULL, s.k_th, s.k_td, s.k_pd, F.Xh, F.Xd, F.Xp);
+    const bool no_cosine = o.cosine != 0;
+    const bool live = s.live;
+    double gi[3], go[3];
+    through_normalisation(s.a, s.in_dir.rs, u.ax, u.ay, u.az, (double)s.kappa, gi);
+    through_normalisation(s.b, s.out_dir.rs, u.bx, u.by, u.bz, (double)s.kappa, go);
+    go[2] += no_cosine ? 0.0 : F.V;
+    TableDirGrad r;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        r.wi[k] = live ? finite_f32(gi[k]) : 0.0f;
+        r.wo[k] = live ? finite_f32(go[k]) : 0.0f;
+    }
+    return r;
+}
+
 // grad_wi = sum_c g_c dE_c / d wi and grad_wo of ONE unit on the RGB table m (kind MERL / TABLE, its texels in layout LAYOUT) under the
 // options o (lookup, node, cosine; negative is a property of the stored texels here).  Dead units — eval's: wi.z <= 0, wo.z <= 0, a
 // NaN / inf component — get +0.0f from a select at the very end, whatever g holds.
@@ -152,25 +241,9 @@ MRL_HD TableDirGrad table_eval_dir_grad(const MaterialDev &m, const Options &o, 
                                         const float g32[3])
 {
 #pragma clang fp contract(off)
-    const TableMaps maps(m);
-    const Dir in_dir = dir_f32(wix, wiy, wiz), out_dir = dir_f32(wox, woy, woz);
-    const Vec3 a = unit(in_dir), b = unit(out_dir);
-    const Coords c = maps(normalize_f32(wix, wiy, wiz), out_dir);           // eval's own coordinates: they select the cell
-    const bool trilinear = o.lookup != 0, periodic = param_phi_periodic(m.param);
-    const double shift = (trilinear && o.node) ? 0.5 : 0.0;
-    const double xh = c.xh - shift, xd = c.xd - shift, xp = c.xp - shift;
-    int h0, d0, p0;
-    double fh, fd, fp;
-    split_clamped(xh, m.n_th, h0, fh);
-    split_clamped(xd, m.n_td, d0, fd);
-    split_phi(periodic, xp, m.n_pd, p0, fp);
-    // a nearest lookup: lookup_nearest_t's cell, no fractions
-    h0 = trilinear ? h0 : trunc_i(c.xh); d0 = trilinear ? d0 : trunc_i(c.xd); p0 = trilinear ? p0 : trunc_i(c.xp);
-    fh = trilinear ? fh : 0.0; fd = trilinear ? fd : 0.0; fp = trilinear ? fp : 0.0;
-    // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table
-    h0 = clampi(h0, 0, m.n_th - 1); d0 = clampi(d0, 0, m.n_td - 1); p0 = clampi(p0, 0, m.n_pd - 1);
+    const DirCell s = dir_cell(m, o, wix, wiy, wiz, wox, woy, woz);
     float f[24];
-    load_cell<LAYOUT>(m, h0, d0, p0, f);
+    load_cell<LAYOUT>(m, s.h0, s.d0, s.p0, f);
 
     // 1. per channel the seven exact differences to corner 0, u_k[c] = f[k][c] - f[0][c], contracted with g: t_k = sum_c g_c u_k[c] (t_0 = 0).
     //    V is sum_c g_c f[0][c] plus the trilinear form of the t_k, the three D_axis the bilinear forms of their differences
@@ -181,38 +254,9 @@ MRL_HD TableDirGrad table_eval_dir_grad(const MaterialDev &m, const Options &o, 
 #pragma unroll
     for (int k = 1; k < 8; ++k)
         t[k] = __builtin_fma(g[2], (double)f[3 * k + 2] - b2, __builtin_fma(g[1], (double)f[3 * k + 1] - b1, g[0] * ((double)f[3 * k] - b0)));
-    const double gh = 1.0 - fh, gd = 1.0 - fd, gp = 1.0 - fp;
-    const double V = __builtin_fma(g[2], b2, __builtin_fma(g[1], b1, g[0] * b0)) +
-                     lerp_fma(gh, fh, lerp_fma(gd, fd, fp * t[1], lerp_fma(gp, fp, t[2], t[3])),
-                              lerp_fma(gd, fd, lerp_fma(gp, fp, t[4], t[5]), lerp_fma(gp, fp, t[6], t[7])));
-    // corners (k, k + 1) along the azimuth, (k, k + 2) along axis 1, (k, k + 4) along axis 0
-    const double Dp = lerp_fma(gh, fh, lerp_fma(gd, fd, t[1], t[3] - t[2]), lerp_fma(gd, fd, t[5] - t[4], t[7] - t[6]));
-    const double Dd = lerp_fma(gh, fh, lerp_fma(gp, fp, t[2], t[3] - t[1]), lerp_fma(gp, fp, t[6] - t[4], t[7] - t[5]));
-    const double Dh = lerp_fma(gd, fd, lerp_fma(gp, fp, t[4], t[5] - t[1]), lerp_fma(gp, fp, t[6] - t[2], t[7] - t[3]));
-    // df / dx is 1 inside the cell; 0 under an active lower clamp (the upper end has equal texels: its D is 0) and for nearest
-    const double Xh = (trilinear && xh >= 0.0) ? Dh : 0.0;
-    const double Xd = (trilinear && xd >= 0.0) ? Dd : 0.0;
-    const double Xp = (trilinear && (periodic || xp >= 0.0)) ? Dp : 0.0;
-
-    // 2. through the coordinate map (a wave-uniform branch for a single-material launch)
-    const UnitAdjoint u = m.param == PARAM_HALF_DIFF ? pull_half_diff(a, b, maps.k_th, maps.k_td, maps.k_pd, c.xh, Xh, Xd, Xp)
-                                                     : pull_standard(a, b, m.param == PARAM_STANDARD_FULL, maps.k_th, maps.k_td, maps.k_pd, Xh, Xd, Xp);
-
-    // 3. through the normalisations and the cosine factor: kappa is eval_tail's Float wo.z (or 1; NaN when an input is not finite)
-    const bool no_cosine = o.cosine != 0;
-    const float kappa = cos_or_nan32((wix + wiy + wiz), wox, woy, woz, no_cosine);
-    const bool live = (wiz > 0.0f) && (woz > 0.0f) && (kappa == kappa);
-    double gi[3], go[3];
-    through_normalisation(a, in_dir.rs, u.ax, u.ay, u.az, (double)kappa, gi);
-    through_normalisation(b, out_dir.rs, u.bx, u.by, u.bz, (double)kappa, go);
-    go[2] += no_cosine ? 0.0 : V;
-    TableDirGrad r;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        r.wi[k] = live ? finite_f32(gi[k]) : 0.0f;
-        r.wo[k] = live ? finite_f32(go[k]) : 0.0f;
-    }
-    return r;
+    const DirForms F = dir_forms(s, t, __builtin_fma(g[2], b2, __builtin_fma(g[1], b1, g[0] * b0)));
+    // 2. through the coordinate map, 3. through the normalisations and the cosine factor
+    return dir_tail(m.param, o, s, F);
 }
 
 } // namespace fast

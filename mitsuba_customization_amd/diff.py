@@ -7,7 +7,8 @@ tables (include/merl_hip_diff_table.h, mrl_table_grad_dir_batch)
 
 the gradient has flowed through eval into whatever produced wi and wo — a shading-frame rotation, a normal map, a camera pose.  The
 gradient in the material's own parameters is MerlHip.ggx_grad, in a table's texels MerlHip.table_grad (fit.py).  table_eval is the
-same on a table material, and eval serves either kind and batches that mix them."""
+same on a table material, and eval serves either kind and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
+tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels]."""
 import torch
 
 from . import host
@@ -73,6 +74,26 @@ class _GgxEval(torch.autograd.Function):
         return grads.get("wi"), grads.get("wo"), None, None, None
 
 
+class _EvalNch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wi, wo, gpu, n_channels, mat, material):
+        wi, wo = wi.contiguous(), wo.contiguous()
+        ctx.save_for_backward(wi, wo)
+        ctx.gpu, ctx.n_channels, ctx.mat, ctx.material = gpu, n_channels, mat, material
+        return gpu.eval_nch(wi, wo, n_channels, mat=mat, material=material)
+
+    @staticmethod
+    def backward(ctx, grad_values):
+        wi, wo = ctx.saved_tensors
+        # only what the graph asks for: the other output pointer is NULL and that gradient is neither computed nor written
+        want = tuple(name for name, needed in zip(("wi", "wo"), ctx.needs_input_grad[:2]) if needed)
+        grads = {}
+        if want:
+            out = ctx.gpu.table_grad_dir_nch(wi, wo, grad_values.contiguous(), ctx.n_channels, mat=ctx.mat, material=ctx.material, want=want)
+            grads = dict(zip(want, out if len(want) == 2 else (out,)))
+        return grads.get("wi"), grads.get("wo"), None, None, None, None
+
+
 def ggx_eval(ctx, wi, wo, mat=None, material: int = 0):
     """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be GGX conductors:
     the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no live GGX
@@ -94,3 +115,11 @@ def eval(ctx, wi, wo, mat=None, material: int = 0):
     ggx_grad_dir, each exactly zero on the other's units; units of kinds with no gradient (n-channel, RGL, spectral, released or
     unknown ids) receive zeros."""
     return _Eval.apply(wi, wo, ctx, mat, material, _any_backward)
+
+
+def table_eval_nch(ctx, wi, wo, n_channels: int, mat=None, material: int = 0):
+    """MerlHip.eval_nch(wi, wo, n_channels, mat, material) of the context `ctx` — [n, n_channels] values —, differentiable in wi and wo.
+    The materials must be n-channel tables of exactly n_channels channels: the backward pass of a single material of another kind or
+    width raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no such table receives a zero gradient.  One
+    MerlHip.table_grad_dir_nch call for what the graph needs (include/merl_hip_diff_nch.h)."""
+    return _EvalNch.apply(wi, wo, ctx, n_channels, mat, material)

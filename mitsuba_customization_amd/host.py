@@ -72,6 +72,8 @@ FIT_ABI_SYMBOLS = ("mrl_ggx_grad_batch",)
 DIFF_ABI_SYMBOLS = ("mrl_ggx_grad_dir_batch", "mrl_ggx_grad_dir_queue")
 # every symbol include/merl_hip_diff_table.h declares: the direction gradient of eval on RGB table materials
 DIFF_TABLE_ABI_SYMBOLS = ("mrl_table_grad_dir_batch", "mrl_table_grad_dir_queue")
+# every symbol include/merl_hip_diff_nch.h declares: the same gradient on n-channel table materials
+DIFF_NCH_ABI_SYMBOLS = ("mrl_table_grad_dir_batch_nch", "mrl_table_grad_dir_queue_nch")
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -275,6 +277,8 @@ def load_library(path: Optional[str] = None):
     L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
     L.mrl_table_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_table_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
+    L.mrl_table_grad_dir_batch_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp, fp]
+    L.mrl_table_grad_dir_queue_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp, fp]
     L.mrl_generate_pairs.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, fp, fp, fp]
     L.mrl_generate_materials.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, vp]
     L.mrl_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -839,6 +843,21 @@ class MerlHip:
                     "mrl_table_grad_dir_batch")
         return outs[0] if len(outs) == 1 else outs
 
+    def table_grad_dir_nch(self, wi, wo, grad_values, n_channels: int, mat=None, material: int = 0, want=("wi", "wo"), out=None):
+        """The direction gradient of eval_nch on n-channel table materials (mrl_table_grad_dir_batch_nch, include/merl_hip_diff_nch.h):
+        per unit grad_wi = sum_c grad_values_c d eval_c / d wi over the n_channels channels and the same in wo, [n, 3] f32, overwritten;
+        grad_values: [n, n_channels] f32.  A dead unit, and with mat= a unit whose id names no live table of exactly n_channels
+        channels, gets zeros.  Same conventions as ggx_grad_dir()."""
+        n = int(wi.shape[0]); self._prep(wi)
+        c = int(n_channels)
+        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._empty)
+        self._check(self._lib.mrl_table_grad_dir_batch_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                                           _addr(grad_values, np.float32, max(c, 1), n, "grad_values"),
+                                                           _addr(mat, np.int32, None, n, "mat"), material, n, c,
+                                                           _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
+                    "mrl_table_grad_dir_batch_nch")
+        return outs[0] if len(outs) == 1 else outs
+
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
 
@@ -910,6 +929,21 @@ class MerlHip:
                                                        _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material,
                                                        q, q_count, cap, _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
                     "mrl_table_grad_dir_queue")
+        return outs[0] if len(outs) == 1 else outs
+
+    def table_grad_dir_queue_nch(self, wi, wo, grad_values, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None,
+                                 want=("wi", "wo"), out=None):
+        """table_grad_dir_nch() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_dir_queue_nch); other slots of `out` stay
+        as they are (outputs allocated here start from zeros)."""
+        n = int(wi.shape[0])
+        c = int(n_channels)
+        q, q_count, cap = self._queue(wi, queue, count, capacity)
+        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._zeros)
+        self._check(self._lib.mrl_table_grad_dir_queue_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                                           _addr(grad_values, np.float32, max(c, 1), n, "grad_values"),
+                                                           _addr(mat, np.int32, None, n, "mat"), material, q, q_count, cap, c,
+                                                           _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
+                    "mrl_table_grad_dir_queue_nch")
         return outs[0] if len(outs) == 1 else outs
 
     def pdf_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
