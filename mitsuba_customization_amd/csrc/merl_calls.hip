@@ -260,6 +260,54 @@ int run_queue(mrl_ctx *ctx, const BatchCall &c, const uint32_t *queue, const uin
     return launch_device(ctx, c, queue, queue_count);
 }
 
+// mrl_*_grad_dir_batch / _queue of every family (DirGradFamily); queued: over queue[0 .. min(*queue_count, n)), n its capacity
+int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f)
+{
+    MRL_GUARD(ctx);
+    if (c.n == 0) return MRL_OK;
+    if (c.queued && (!c.queue || !c.queue_count)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
+    StreamList streams = { { (void *)c.wi, 12, false, "wi" }, { (void *)c.wo, 12, false, "wo" }, { (void *)c.g, f.g_bytes, false, f.g_name } };
+    if (first_null(streams)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
+    if (!c.grad_wi && !c.grad_wo) return fail(ctx, MRL_ERR_INVALID, "grad_wi and grad_wo are both null");
+    int at_mat = -1, at_wi = -1, at_wo = -1;
+    if (c.mat) { at_mat = (int)streams.size(); streams.push_back({ (void *)c.mat, 4, false, "mat" }); }
+    if (c.grad_wi) { at_wi = (int)streams.size(); streams.push_back({ c.grad_wi, 12, true, "grad_wi" }); }
+    if (c.grad_wo) { at_wo = (int)streams.size(); streams.push_back({ c.grad_wo, 12, true, "grad_wo" }); }
+    if (ctx->materials.empty()) return fail(ctx, MRL_ERR_MATERIAL, "no material loaded");
+    if (!c.mat) {
+        if (c.single_id < 0 || (size_t)c.single_id >= ctx->materials.size() || ctx->materials[(size_t)c.single_id].released)
+            return fail(ctx, MRL_ERR_MATERIAL, "unknown material id");
+        if (!f.evaluates(ctx->materials[(size_t)c.single_id])) return fail(ctx, MRL_ERR_MATERIAL, f.not_evaluated);
+    }
+    if (f.refuses_renormalise && ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
+        return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise: the direction gradient of the renormalising blend is not offered");
+    if (c.queued && c.n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
+    MRL_HIP(ctx, hipSetDevice(ctx->device));
+    const int kind = c.queued ? common_kind({ c.queue, c.queue_count }, streams) : common_kind({}, streams);
+    if (c.queued && kind != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
+    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
+
+    mrl::BatchArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.materials = ctx->d_materials;
+    a.n_materials = (int)ctx->materials.size();
+    a.safe = tombstone_dev(ctx);
+    a.single = c.mat ? f.single_with_ids() : ctx->materials[(size_t)c.single_id].dev;
+    a.opts = ctx->opts;
+    a.idx = c.queue; a.idx_count = c.queue_count;
+    if (kind == 1) {
+        a.wi = c.wi; a.wo = c.wo; a.mat = c.mat; a.n = c.n;
+        MRL_HIP(ctx, f.launch(a, c.g, c.grad_wi, c.grad_wo));
+        return MRL_OK;
+    }
+    return run_host_staged(ctx, streams, c.n, 0, [&](char *const *addr, size_t m) -> int {
+        a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.n = m;
+        a.mat = at_mat >= 0 ? (const int32_t *)addr[at_mat] : nullptr;
+        MRL_HIP(ctx, f.launch(a, (const float *)addr[2], at_wi >= 0 ? (float *)addr[at_wi] : nullptr, at_wo >= 0 ? (float *)addr[at_wo] : nullptr));
+        return MRL_OK;
+    });
+}
+
 } // namespace mrlabi
 using namespace mrlabi;
 

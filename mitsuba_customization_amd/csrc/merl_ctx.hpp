@@ -2,12 +2,15 @@
 // error / lock macros and the internal functions one file defines and another calls.  Not installed; nothing here is part of the ABI.
 //   merl_abi.hip           contexts, options, streams, memory helpers, one-unit call service, errors
 //   merl_materials.hip     material constructors (MERL / customized_measurement / n-channel / GGX / RGL), release, host images
-//   merl_calls.hip         batch, queue and n-channel calls: a call's arrays as a stream list, the two host-array movers, launches
+//   merl_calls.hip         batch, queue and n-channel calls: a call's arrays as a stream list, the two host-array movers, launches;
+//                          grad_dir_call, the host side of every direction-gradient call
 //   merl_host_stage.hpp    host-array path, host C++ only: stream list, slot layout, the chunk loop, the copy threads
 //   merl_image_cache.hip   on-disk cache of a material's device image
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
 //   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
+//   merl_dir_grad.hpp      what the direction-gradient kernels share: the grid-stride loop with its masked stores, the record a
+//                          material id names, the PER_LANE / INDEXED dispatch; their one host call is grad_dir_call of merl_calls.hip
 //   merl_ggx_dir_grad.hip  the direction gradient of eval on GGX conductors (mrl_ggx_grad_dir_batch / _queue): streaming kernel + calls
 //   merl_table_dir_grad.hip  the same on RGB tables (mrl_table_grad_dir_batch / _queue)
 //   merl_nch_dir_grad.hip  the same on n-channel tables (mrl_table_grad_dir_batch_nch / _queue_nch)
@@ -190,6 +193,29 @@ mrl::BatchArgs batch_args(const mrl_ctx *ctx, const BatchCall &c);           // 
 using HostLaunch = std::function<int(char *const *addr, size_t m)>;
 // host arrays through the context's stage buffer, one chunk at a time (cap_bytes > 0: chunks so small that the slot stays below it)
 int run_host_staged(mrl_ctx *ctx, const StreamList &streams, size_t n, size_t cap_bytes, const HostLaunch &launch);
+
+// A direction-gradient call (include/merl_hip_diff*.h), whole arrays or a queue, and what its family of materials supplies
+struct DirGradCall {
+    const float *wi, *wo, *g;
+    const int32_t *mat;
+    int32_t single_id;
+    size_t n;                                    // units; queued: the queue's capacity
+    bool queued;
+    const uint32_t *queue, *queue_count;
+    float *grad_wi, *grad_wo;                    // either may be null, not both
+};
+struct DirGradFamily {
+    size_t g_bytes;                              // of g per unit
+    const char *g_name;
+    std::function<bool(const MaterialHost &)> evaluates;     // a call without ids: is its material one of the family's?
+    std::string not_evaluated;                   // the MRL_ERR_MATERIAL message if it is not
+    bool refuses_renormalise;                    // MRL_OPT_NEGATIVE = renormalise: MRL_ERR_INVALID
+    std::function<mrl::MaterialDev()> single_with_ids;       // BatchArgs::single of a launch with ids: what a unit of another id reads
+    // the family's kernel on device-accessible arrays; a: everything but the outputs
+    std::function<hipError_t(const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo)> launch;
+};
+// checks in the order the headers document, then f.launch on the caller's device arrays or chunk by chunk on staged host arrays
+int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f);
 
 // ---- merl_abi.hip ----
 // a non-blocking stream whose kernels may use all but `reserved` of the device's `device_cus` compute units (reserved = 0: a plain

@@ -9,13 +9,11 @@ the gradient has flowed through eval into whatever produced wi and wo — a shad
 gradient in the material's own parameters is MerlHip.ggx_grad, in a table's texels MerlHip.table_grad (fit.py).  table_eval is the
 same on a table material, and eval serves either kind and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
 tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels]."""
+from functools import partial
+
 import torch
 
 from . import host
-
-
-def _table_backward(gpu, *args, **kw):
-    return gpu.table_grad_dir(*args, **kw)
 
 
 def _any_backward(gpu, wi, wo, grad_rgb, mat=None, material=0, want=("wi", "wo")):
@@ -34,53 +32,13 @@ def _any_backward(gpu, wi, wo, grad_rgb, mat=None, material=0, want=("wi", "wo")
 
 
 class _Eval(torch.autograd.Function):
-    """backward_call(gpu, wi, wo, grad_rgb, mat=, material=, want=) is one of the three functions above"""
+    """forward_call(wi, wo): an eval of the host; backward_call(wi, wo, grad, want=): the direction gradient of that eval"""
     @staticmethod
-    def forward(ctx, wi, wo, gpu, mat, material, backward_call):
+    def forward(ctx, wi, wo, forward_call, backward_call):
         wi, wo = wi.contiguous(), wo.contiguous()
         ctx.save_for_backward(wi, wo)
-        ctx.gpu, ctx.mat, ctx.material, ctx.backward_call = gpu, mat, material, backward_call
-        return gpu.eval(wi, wo, mat=mat, material=material)
-
-    @staticmethod
-    def backward(ctx, grad_rgb):
-        wi, wo = ctx.saved_tensors
-        # only what the graph asks for: the other output pointer is NULL and that gradient is neither computed nor written
-        want = tuple(name for name, needed in zip(("wi", "wo"), ctx.needs_input_grad[:2]) if needed)
-        grads = {}
-        if want:
-            out = ctx.backward_call(ctx.gpu, wi, wo, grad_rgb.contiguous(), mat=ctx.mat, material=ctx.material, want=want)
-            grads = dict(zip(want, out if len(want) == 2 else (out,)))
-        return grads.get("wi"), grads.get("wo"), None, None, None, None
-
-
-class _GgxEval(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, wi, wo, gpu, mat, material):
-        wi, wo = wi.contiguous(), wo.contiguous()
-        ctx.save_for_backward(wi, wo)
-        ctx.gpu, ctx.mat, ctx.material = gpu, mat, material
-        return gpu.eval(wi, wo, mat=mat, material=material)
-
-    @staticmethod
-    def backward(ctx, grad_rgb):
-        wi, wo = ctx.saved_tensors
-        # only what the graph asks for: the other output pointer is NULL and that gradient is neither computed nor written
-        want = tuple(name for name, needed in zip(("wi", "wo"), ctx.needs_input_grad[:2]) if needed)
-        grads = {}
-        if want:
-            out = ctx.gpu.ggx_grad_dir(wi, wo, grad_rgb.contiguous(), mat=ctx.mat, material=ctx.material, want=want)
-            grads = dict(zip(want, out if len(want) == 2 else (out,)))
-        return grads.get("wi"), grads.get("wo"), None, None, None
-
-
-class _EvalNch(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, wi, wo, gpu, n_channels, mat, material):
-        wi, wo = wi.contiguous(), wo.contiguous()
-        ctx.save_for_backward(wi, wo)
-        ctx.gpu, ctx.n_channels, ctx.mat, ctx.material = gpu, n_channels, mat, material
-        return gpu.eval_nch(wi, wo, n_channels, mat=mat, material=material)
+        ctx.backward_call = backward_call
+        return forward_call(wi, wo)
 
     @staticmethod
     def backward(ctx, grad_values):
@@ -89,16 +47,16 @@ class _EvalNch(torch.autograd.Function):
         want = tuple(name for name, needed in zip(("wi", "wo"), ctx.needs_input_grad[:2]) if needed)
         grads = {}
         if want:
-            out = ctx.gpu.table_grad_dir_nch(wi, wo, grad_values.contiguous(), ctx.n_channels, mat=ctx.mat, material=ctx.material, want=want)
+            out = ctx.backward_call(wi, wo, grad_values.contiguous(), want=want)
             grads = dict(zip(want, out if len(want) == 2 else (out,)))
-        return grads.get("wi"), grads.get("wo"), None, None, None, None
+        return grads.get("wi"), grads.get("wo"), None, None
 
 
 def ggx_eval(ctx, wi, wo, mat=None, material: int = 0):
     """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be GGX conductors:
     the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no live GGX
     material receives a zero gradient."""
-    return _GgxEval.apply(wi, wo, ctx, mat, material)
+    return _Eval.apply(wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.ggx_grad_dir, mat=mat, material=material))
 
 
 def table_eval(ctx, wi, wo, mat=None, material: int = 0):
@@ -106,7 +64,7 @@ def table_eval(ctx, wi, wo, mat=None, material: int = 0):
     customized_measurement): the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose
     id names no live RGB table receives a zero gradient.  The gradient is the one of the trilinear interpolant in the cell eval
     selects (include/merl_hip_diff_table.h): piecewise smooth, like the function."""
-    return _Eval.apply(wi, wo, ctx, mat, material, _table_backward)
+    return _Eval.apply(wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.table_grad_dir, mat=mat, material=material))
 
 
 def eval(ctx, wi, wo, mat=None, material: int = 0):
@@ -114,7 +72,7 @@ def eval(ctx, wi, wo, mat=None, material: int = 0):
     Single material: the backward pass is the gradient call of that material's kind.  With mat=: the sum of table_grad_dir and
     ggx_grad_dir, each exactly zero on the other's units; units of kinds with no gradient (n-channel, RGL, spectral, released or
     unknown ids) receive zeros."""
-    return _Eval.apply(wi, wo, ctx, mat, material, _any_backward)
+    return _Eval.apply(wi, wo, partial(ctx.eval, mat=mat, material=material), partial(_any_backward, ctx, mat=mat, material=material))
 
 
 def table_eval_nch(ctx, wi, wo, n_channels: int, mat=None, material: int = 0):
@@ -122,4 +80,5 @@ def table_eval_nch(ctx, wi, wo, n_channels: int, mat=None, material: int = 0):
     The materials must be n-channel tables of exactly n_channels channels: the backward pass of a single material of another kind or
     width raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no such table receives a zero gradient.  One
     MerlHip.table_grad_dir_nch call for what the graph needs (include/merl_hip_diff_nch.h)."""
-    return _EvalNch.apply(wi, wo, ctx, n_channels, mat, material)
+    return _Eval.apply(wi, wo, partial(ctx.eval_nch, n_channels=n_channels, mat=mat, material=material),
+                       partial(ctx.table_grad_dir_nch, n_channels=n_channels, mat=mat, material=material))

@@ -818,45 +818,39 @@ class MerlHip:
         by_name = dict(zip(want, outs))
         return by_name.get("wi"), by_name.get("wo"), outs
 
+    def _grad_dir_call(self, symbol, wi, wo, g, mat, material, want, out, n_channels=None, queue=None):
+        """One direction-gradient call.  g: [n, 3] "grad_rgb", or with n_channels [n, n_channels] "grad_values"; queue: the (queue,
+        count, capacity) of a *_queue symbol, whose outputs allocated here start from zeros.  Returns the gradient wanted, or both."""
+        n = int(wi.shape[0])
+        if queue is None:
+            self._prep(wi)
+        name, cols, channels = ("grad_rgb", 3, ()) if n_channels is None else ("grad_values", max(int(n_channels), 1), (int(n_channels),))
+        middle = (n,) if queue is None else self._queue(wi, *queue)
+        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._empty if queue is None else self._zeros)
+        self._check(getattr(self._lib, symbol)(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                               _addr(g, np.float32, cols, n, name), _addr(mat, np.int32, None, n, "mat"), material, *middle, *channels,
+                                               _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")), symbol)
+        return outs[0] if len(outs) == 1 else outs
+
     def ggx_grad_dir(self, wi, wo, grad_rgb, mat=None, material: int = 0, want=("wi", "wo"), out=None):
         """The direction gradient of eval on GGX materials (mrl_ggx_grad_dir_batch): per unit grad_wi = sum_c grad_rgb_c d eval_c / d wi
         and the same in wo, [n, 3] f32, overwritten; a dead unit, and with mat= a unit whose id names no live GGX material, gets
         zeros.  want: which of the two to compute.  numpy in -> numpy out, device tensors in -> device tensors out.  Returns the
         gradient wanted, or (grad_wi, grad_wo)."""
-        n = int(wi.shape[0]); self._prep(wi)
-        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._empty)
-        self._check(self._lib.mrl_ggx_grad_dir_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                     _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material, n,
-                                                     _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
-                    "mrl_ggx_grad_dir_batch")
-        return outs[0] if len(outs) == 1 else outs
+        return self._grad_dir_call("mrl_ggx_grad_dir_batch", wi, wo, grad_rgb, mat, material, want, out)
 
     def table_grad_dir(self, wi, wo, grad_rgb, mat=None, material: int = 0, want=("wi", "wo"), out=None):
         """The direction gradient of eval on RGB table materials (mrl_table_grad_dir_batch, include/merl_hip_diff_table.h): per unit
         grad_wi = sum_c grad_rgb_c d eval_c / d wi and the same in wo, [n, 3] f32, overwritten; a dead unit, and with mat= a unit whose
         id names no live RGB table, gets zeros.  Same conventions as ggx_grad_dir()."""
-        n = int(wi.shape[0]); self._prep(wi)
-        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._empty)
-        self._check(self._lib.mrl_table_grad_dir_batch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                       _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material, n,
-                                                       _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
-                    "mrl_table_grad_dir_batch")
-        return outs[0] if len(outs) == 1 else outs
+        return self._grad_dir_call("mrl_table_grad_dir_batch", wi, wo, grad_rgb, mat, material, want, out)
 
     def table_grad_dir_nch(self, wi, wo, grad_values, n_channels: int, mat=None, material: int = 0, want=("wi", "wo"), out=None):
         """The direction gradient of eval_nch on n-channel table materials (mrl_table_grad_dir_batch_nch, include/merl_hip_diff_nch.h):
         per unit grad_wi = sum_c grad_values_c d eval_c / d wi over the n_channels channels and the same in wo, [n, 3] f32, overwritten;
         grad_values: [n, n_channels] f32.  A dead unit, and with mat= a unit whose id names no live table of exactly n_channels
         channels, gets zeros.  Same conventions as ggx_grad_dir()."""
-        n = int(wi.shape[0]); self._prep(wi)
-        c = int(n_channels)
-        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._empty)
-        self._check(self._lib.mrl_table_grad_dir_batch_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                           _addr(grad_values, np.float32, max(c, 1), n, "grad_values"),
-                                                           _addr(mat, np.int32, None, n, "mat"), material, n, c,
-                                                           _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
-                    "mrl_table_grad_dir_batch_nch")
-        return outs[0] if len(outs) == 1 else outs
+        return self._grad_dir_call("mrl_table_grad_dir_batch_nch", wi, wo, grad_values, mat, material, want, out, n_channels)
 
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
@@ -910,41 +904,18 @@ class MerlHip:
     def ggx_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
         """ggx_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_grad_dir_queue); other slots of `out` stay as they
         are (outputs allocated here start from zeros)."""
-        n = int(wi.shape[0])
-        q, q_count, cap = self._queue(wi, queue, count, capacity)
-        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._zeros)
-        self._check(self._lib.mrl_ggx_grad_dir_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                     _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material,
-                                                     q, q_count, cap, _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
-                    "mrl_ggx_grad_dir_queue")
-        return outs[0] if len(outs) == 1 else outs
+        return self._grad_dir_call("mrl_ggx_grad_dir_queue", wi, wo, grad_rgb, mat, material, want, out, queue=(queue, count, capacity))
 
     def table_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
         """table_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_dir_queue); other slots of `out` stay as
         they are (outputs allocated here start from zeros)."""
-        n = int(wi.shape[0])
-        q, q_count, cap = self._queue(wi, queue, count, capacity)
-        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._zeros)
-        self._check(self._lib.mrl_table_grad_dir_queue(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                       _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), _addr(mat, np.int32, None, n, "mat"), material,
-                                                       q, q_count, cap, _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
-                    "mrl_table_grad_dir_queue")
-        return outs[0] if len(outs) == 1 else outs
+        return self._grad_dir_call("mrl_table_grad_dir_queue", wi, wo, grad_rgb, mat, material, want, out, queue=(queue, count, capacity))
 
     def table_grad_dir_queue_nch(self, wi, wo, grad_values, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None,
                                  want=("wi", "wo"), out=None):
         """table_grad_dir_nch() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_dir_queue_nch); other slots of `out` stay
         as they are (outputs allocated here start from zeros)."""
-        n = int(wi.shape[0])
-        c = int(n_channels)
-        q, q_count, cap = self._queue(wi, queue, count, capacity)
-        gwi, gwo, outs = self._grad_dir_outputs(wi, want, out, self._zeros)
-        self._check(self._lib.mrl_table_grad_dir_queue_nch(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
-                                                           _addr(grad_values, np.float32, max(c, 1), n, "grad_values"),
-                                                           _addr(mat, np.int32, None, n, "mat"), material, q, q_count, cap, c,
-                                                           _addr(gwi, np.float32, 3, n, "grad_wi"), _addr(gwo, np.float32, 3, n, "grad_wo")),
-                    "mrl_table_grad_dir_queue_nch")
-        return outs[0] if len(outs) == 1 else outs
+        return self._grad_dir_call("mrl_table_grad_dir_queue_nch", wi, wo, grad_values, mat, material, want, out, n_channels, (queue, count, capacity))
 
     def pdf_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
         return _stream_call(self, "queue", "pdf", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
