@@ -1,24 +1,14 @@
 // merl_dir_grad.hpp — what the direction-gradient kernels share (merl_ggx_dir_grad.hip, merl_table_dir_grad.hip, merl_nch_dir_grad.hip;
-// DESIGN.md §5i - §5k): the arrays beside BatchArgs, the material record a unit's id names, the grid-stride loop with its masked
-// stores, and the choice of PER_LANE / INDEXED at a launch.  The host call that ends in these launches is grad_dir_call of
-// merl_calls.hip.  Each family keeps its __global__ kernel, its launch bounds and its per-lane function.
+// DESIGN.md §5i - §5k): the arrays beside BatchArgs and the grid-stride loop with its masked stores.  The material record a unit's
+// id names is lane_material of merl_unit.hpp; a.mat, a.idx -> PER_LANE, INDEXED at a launch is with_flags of merl_kernels.hpp.  The
+// host call that ends in these launches is grad_dir_call of merl_calls.hip.  Each family keeps its __global__ kernel, its launch
+// bounds and its per-lane function.
 #pragma once
-#include "merl_kernels.hpp"
-
-#include <type_traits>
+#include "merl_unit.hpp"
 
 namespace mrl {
 
 struct DirGradOut { const float *g; float *grad_wi, *grad_wo; };     // g: [n][3], or [n][n_ch] for the n-channel kernels
-
-// the record mat[i] names; an id out of range: record 0 and in_range = false, so that the caller's loads stay branch-free
-struct LaneMaterial { const MaterialDev &m; bool in_range; };
-__device__ __forceinline__ LaneMaterial lane_material(const BatchArgs &a, size_t i)
-{
-    const int id = a.mat[i];
-    const bool in_range = id >= 0 && id < a.n_materials;
-    return { a.materials[in_range ? id : 0], in_range };
-}
 
 // The body of a direction-gradient kernel of BLOCK threads: a grid-stride loop over the units (INDEXED: over a.idx), one lane = one
 // unit.  unit(i, out_wi, out_wo) fills the two gradients of unit i and says whether its material is one the family evaluates; the
@@ -42,18 +32,6 @@ __device__ __forceinline__ void dir_grad_loop(const BatchArgs &a, const DirGradO
             store3s<true>(o.grad_wo, i, v);
         }
     }
-}
-
-// f(per_lane, indexed), two std::bool_constant: a.mat — a material id per unit —, a.idx — the launch walks a queue
-template <class F>
-void dispatch_ids_queue(const BatchArgs &a, F &&f)
-{
-    auto with_ids = [&](auto per_lane) {
-        if (a.idx) f(per_lane, std::true_type{});
-        else f(per_lane, std::false_type{});
-    };
-    if (a.mat) with_ids(std::true_type{});
-    else with_ids(std::false_type{});
 }
 
 } // namespace mrl

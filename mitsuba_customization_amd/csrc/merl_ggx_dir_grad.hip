@@ -57,9 +57,8 @@ __global__ __launch_bounds__(kDirBlock, kDirBlocksPerCu) void k_ggx_grad_dir(Bat
 hipError_t launch_ggx_grad_dir(const BatchArgs &a, const DirGradOut &o, int compute_units, hipStream_t stream)
 {
     const dim3 grid(grid_blocks(a.n, kDirBlock, (size_t)std::max(compute_units, 1) * kDirBlocksPerCu)), block(kDirBlock);
-    dispatch_ids_queue(a, [&](auto per_lane, auto indexed) {
-        hipLaunchKernelGGL((k_ggx_grad_dir<decltype(per_lane)::value, decltype(indexed)::value>), grid, block, 0, stream, a, o);
-    });
+    with_flags([&](auto per_lane, auto indexed) { hipLaunchKernelGGL((k_ggx_grad_dir<per_lane, indexed>), grid, block, 0, stream, a, o); },
+               a.mat != nullptr, a.idx != nullptr);
     return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@
 #include <cstdio>
 
 #include "merl_kernels.hpp"
-#include "merl_table_fast.hpp"
+#include "merl_unit.hpp"
 #include "merl_ggx_fast.hpp"
 
 namespace mrl {
@@ -31,16 +31,7 @@ __global__ __launch_bounds__(kBlock) void k_batch(BatchArgs a)
     for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < n_items; j += stride) {
         const size_t i = INDEXED ? (size_t)a.idx[j] : j;
         MaterialDev m;
-        bool valid = true;
-        if constexpr (MULTI) {
-            int id = a.mat[i];
-            valid = id >= 0 && id < a.n_materials;
-            m = a.materials[valid ? id : 0];
-            valid = valid && (kind_is_rgb_path(m.kind) || (MODE == MODE_PDF && m.kind == KIND_TABLE_NCH));
-            if (!valid) m = a.safe;
-        } else {
-            m = a.single;
-        }
+        const bool valid = rgb_material<MODE, MULTI>(a, MULTI ? a.mat[i] : 0, m);
         float wix, wiy, wiz;
         load3(a.wi, i, wix, wiy, wiz);
         if (!valid) wiz = 0.0f;                     // unknown material id: every output zero
@@ -74,6 +65,10 @@ __global__ __launch_bounds__(kBlock) void k_table(BatchArgs a)
 {
     const size_t stride = (size_t)gridDim.x * kBlock;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
+        // rgb_material of merl_unit.hpp, written out (through the function the MULTI eval instantiations on bricks allocate 80 VGPRs
+        // instead of 82, another waves-per-SIMD class: profiles/forward_shared_code_ab.txt).  A change to one of its rules is made here
+        // too: the range check with record 0 for an id out of range, the kinds the call evaluates (the RGB path; pdf alone also
+        // n-channel tables), a.safe for everything else, and the caller's wi.z = 0 below.
         MaterialDev m;
         bool known = true;
         if constexpr (MULTI) {
@@ -99,6 +94,7 @@ __global__ __launch_bounds__(kBlock) void k_table(BatchArgs a)
             if constexpr (mode_sample(MODE)) unit_sample(m, a.opts, wix, wiy, wiz, u0, u1, wo2, pdf2, w);
         } else {
             if constexpr (MODE == MODE_PDF) {
+                // (wo_pdf of merl_unit.hpp, written out: wi is normalised only behind the gate)
                 pdf = (wiz > 0.0f && woz > 0.0f) ? woz * kInvPiF : 0.0f;
                 if (a.opts.sampling && pdf > 0.0f)
                     pdf = (float)fast::table_pdf(m, fast::normalize_f32(wix, wiy, wiz), fast::normalize_f32(wox, woy, woz), woz, a.opts.sampling);
@@ -106,8 +102,8 @@ __global__ __launch_bounds__(kBlock) void k_table(BatchArgs a)
                 const fast::Vec3 in = fast::normalize_f32(wix, wiy, wiz);
                 if constexpr (mode_eval(MODE)) fast::unit_eval<LOOKUP, LAYOUT>(m, a.opts, in, wix, wiy, wiz, wox, woy, woz, rgb);
                 if constexpr (mode_pdf(MODE)) {
-                    pdf = (wiz > 0.0f && woz > 0.0f) ? woz * kInvPiF : 0.0f;
-                    if (a.opts.sampling && pdf > 0.0f) pdf = (float)fast::table_pdf(m, in, fast::normalize_f32(wox, woy, woz), woz, a.opts.sampling);
+                    pdf = lambert_pdf(wiz > 0.0f && woz > 0.0f, woz);
+                    pdf = wo_pdf(m, a.opts.sampling, pdf > 0.0f, pdf, in, wox, woy, woz);
                 }
                 if constexpr (mode_sample(MODE)) fast::unit_sample<LOOKUP, LAYOUT>(m, a.opts, in, wix, wiy, wiz, u0, u1, wo2, pdf2, w);
             }
@@ -313,8 +309,7 @@ __device__ __forceinline__ void table_lanes(const BatchArgs &a, const MaterialDe
             fast::eval_tail(v, io.wi_sum, io.wiz, io.wox, io.woy, io.woz, io.rgb, a.opts.cosine != 0);
             if constexpr (mode_pdf(MODE)) {
                 const bool valid = (io.wiz > 0.0f) && (io.woz > 0.0f);
-                io.pdf = valid ? io.woz * kInvPiF : 0.0f;
-                if (a.opts.sampling && valid) io.pdf = (float)fast::table_pdf(m, in, fast::normalize_f32(io.wox, io.woy, io.woz), io.woz, a.opts.sampling);
+                io.pdf = wo_pdf(m, a.opts.sampling, valid, lambert_pdf(valid, io.woz), in, io.wox, io.woy, io.woz);
             }
         }
     }
@@ -437,15 +432,7 @@ __global__ __launch_bounds__(kDmaBlock) void k_table_dma(BatchArgs a)
         const TileIn nxt = request(live_next ? tile_next : tile);
 
         MaterialDev m;
-        bool known = true;
-        if constexpr (MULTI) {
-            known = cur.id >= 0 && cur.id < a.n_materials;
-            m = a.materials[known ? cur.id : 0];
-            known = known && kind_is_rgb_path(m.kind);
-            if (!known) m = a.safe;
-        } else {
-            m = a.single;
-        }
+        const bool known = rgb_material<MODE, MULTI>(a, cur.id, m);
         const bool is_table = !GGX || m.kind != KIND_GGX;
 
         UnitIO io = {};
@@ -513,6 +500,12 @@ __global__ __launch_bounds__(kBlock) void k_ggx(BatchArgs a)
             store3s<NT>(a.out_weight, i, w);
         }
     }
+}
+
+// this lane's rank among the lanes of a ballot mask
+__device__ __forceinline__ unsigned lane_rank(unsigned long long mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 // ---- variant 4: per-kind queues for batches that mix table and analytic materials -----------------
@@ -602,8 +595,8 @@ __global__ __launch_bounds__(kBlock) void k_partition_kinds(const int32_t *mat, 
             t_before += (unsigned)w < wave ? ct : 0u;
             g_before += (unsigned)w < wave ? cg : 0u;
         }
-        if (k.tab) queue_table[t_run + t_before + __builtin_amdgcn_mbcnt_hi((unsigned)(mt >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mt, 0u))] = (uint32_t)i;
-        if (k.ggx) queue_ggx[g_run + g_before + __builtin_amdgcn_mbcnt_hi((unsigned)(mg >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mg, 0u))] = (uint32_t)i;
+        if (k.tab) queue_table[t_run + t_before + lane_rank(mt)] = (uint32_t)i;
+        if (k.ggx) queue_ggx[g_run + g_before + lane_rank(mg)] = (uint32_t)i;
         t_run += t_tile; g_run += g_tile;
         parity ^= 1u;                                         // double-buffered counts: one barrier per tile
     }
@@ -620,11 +613,6 @@ __global__ __launch_bounds__(kBlock) void k_partition_kinds(const int32_t *mat, 
 // turns them into start offsets (one block per material scans its column; a last block lays the materials
 // end to end), pass 3 repeats the walk and writes slot indices to base[k] + offset[chunk][k] + running + rank.
 constexpr int kPartWaves = kBlock / 64;
-
-__device__ __forceinline__ unsigned lane_rank(unsigned long long mask)
-{
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // WRITE = false: count; WRITE = true: scatter slot indices.  table: [chunks][K] counts (pass 1 out) or start offsets (pass 3 in)
 template <bool WRITE>
@@ -723,16 +711,11 @@ __global__ __launch_bounds__(kBlock) void k_build_bricks(const double *planar, i
         float v[32];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int sh = min(ih + (k >> 2), n_th - 1), sd = min(id + ((k >> 1) & 1), n_td - 1), sp = phi_periodic ? (ip + (k & 1)) % n_pd : min(ip + (k & 1), n_pd - 1);
-            const size_t src = ((size_t)sh * n_td + sd) * n_pd + sp;
+            const size_t src = brick_corner(ih, id, ip, k, n_th, n_td, n_pd, phi_periodic);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = scaled_texel(planar, plane, src, ch, scale[ch], clamp);
         }
-#pragma unroll
-        for (int pad = 24; pad < 32; ++pad) v[pad] = 0.0f;
-        float4 *dst = bricks + c * 8;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        store_rgb_brick(bricks + c * 8, v);
     }
 }
 
@@ -764,11 +747,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_to_bricks(const float4 *rows, i
             const float4 t = rows[((ih + (size_t)(k >> 2)) * D + id + (size_t)((k >> 1) & 1)) * P + ip + (size_t)(k & 1)];
             v[3 * k] = t.x; v[3 * k + 1] = t.y; v[3 * k + 2] = t.z;
         }
-#pragma unroll
-        for (int pad = 24; pad < 32; ++pad) v[pad] = 0.0f;
-        float4 *dst = bricks + c * 8;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        store_rgb_brick(bricks + c * 8, v);
     }
 }
 // bricks -> rows: corner 0 of a cell is the cell's own texel; the padding texels repeat the last one / wrap phi as k_build_rows does
@@ -887,15 +866,6 @@ __global__ __launch_bounds__(kBlock) void k_generate_materials(uint64_t seed, ui
 
 // 8 x 256-thread blocks per CU, grid-stride the rest
 inline unsigned grid_for(size_t n, int compute_units) { return grid_blocks(n, kBlock, (size_t)compute_units * 8); }
-
-// runtime flags -> f(std::bool_constant<flag>{}...), the way with_mode turns a mode into a template argument
-template <class F> auto with_flags(F &&f) { return f(); }
-template <class F, class... Rest>
-auto with_flags(F &&f, bool flag, Rest... rest)
-{
-    auto bind = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
-    return flag ? bind(std::true_type{}) : bind(std::false_type{});
-}
 
 template <int MODE>
 hipError_t launch_choice(const KernelChoice &k, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t stream)

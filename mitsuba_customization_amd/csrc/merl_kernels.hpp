@@ -33,6 +33,16 @@ hipError_t with_mode(int mode, F &&f)
     return hipErrorInvalidValue;
 }
 
+// runtime flags -> f(std::bool_constant<flag>{}...), the way with_mode turns a mode into a template argument: every launcher
+// names its kernel once, with `decltype(flag)::value` (or the constant itself) as the template arguments
+template <class F> auto with_flags(F &&f) { return f(); }
+template <class F, class... Rest>
+auto with_flags(F &&f, bool flag, Rest... rest)
+{
+    auto bind = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return flag ? bind(std::true_type{}) : bind(std::false_type{});
+}
+
 // blocks of a grid-stride launch over n units at `threads` per block: at most cap, at least 1; whole_xcds: rounded up to whole
 // rounds over the 8 XCDs (workgroups are dealt to them round-robin; BatchArgs::block_map relies on it)
 inline unsigned grid_blocks(size_t n, size_t threads, size_t cap, bool whole_xcds = false)
@@ -98,6 +108,23 @@ template <bool INDEXED> __device__ __forceinline__ size_t item_count(const Batch
 {
     if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }
     else return a.n;
+}
+
+// ---- table re-layout: what the brick builders share (k_build_bricks, k_rows_to_bricks, k_build_bricks_nch) ----
+// source texel of corner k = 4 a + 2 b + c of cell (ih, id, ip) in a planar [n_th][n_td][n_pd] table: theta_h and theta_d clamp at
+// the last node, phi_d clamps or wraps
+__device__ __forceinline__ size_t brick_corner(int ih, int id, int ip, int k, int n_th, int n_td, int n_pd, int phi_periodic)
+{
+    const int sh = min(ih + (k >> 2), n_th - 1), sd = min(id + ((k >> 1) & 1), n_td - 1), sp = phi_periodic ? (ip + (k & 1)) % n_pd : min(ip + (k & 1), n_pd - 1);
+    return ((size_t)sh * n_td + sd) * n_pd + sp;
+}
+// an RGB brick: 8 corners x 3 channels packed, 8 floats of zero padding -> 128 B
+__device__ __forceinline__ void store_rgb_brick(float4 *dst, float v[32])
+{
+#pragma unroll
+    for (int pad = 24; pad < 32; ++pad) v[pad] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
 
 // ---- which kernel serves a batch launch ----

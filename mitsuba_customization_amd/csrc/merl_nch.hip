@@ -15,7 +15,7 @@
 // that the unit's ds_read_b128 reads are bank-conflict-free — one channel group at a time (LDS: 64 x S x 16 B per wave
 // and lookup; registers hold 4 channels, not n_ch).
 #include "merl_kernels.hpp"
-#include "merl_table_fast.hpp"
+#include "merl_unit.hpp"
 #include "merl_ggx_fast.hpp"
 
 namespace mrl {
@@ -145,15 +145,7 @@ __global__ __launch_bounds__(kNchBlock) void k_table_nch(BatchArgs a, int n_ch)
         const size_t i = INDEXED ? (size_t)a.idx[jj] : jj;
 
         MaterialDev m;
-        bool known = true;
-        if constexpr (MULTI) {
-            const int id = a.mat[i];
-            known = id >= 0 && id < a.n_materials;
-            m = a.materials[known ? id : 0];
-            known = known && m.kind == KIND_TABLE_NCH && m.n_ch == n_ch;
-        } else {
-            m = a.single;
-        }
+        const bool known = nch_material<MULTI>(a, i, n_ch, m);
         // a material this call cannot evaluate: a harmless, valid source (the material array itself) and zero outputs
         const float4 *texels = known ? m.texels : (const float4 *)a.materials;
         const int n_th = known ? m.n_th : 1, n_td = known ? m.n_td : 1, n_pd = known ? m.n_pd : 1;
@@ -218,11 +210,8 @@ __global__ __launch_bounds__(kNchBlock) void k_table_nch(BatchArgs a, int n_ch)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // LDS reads done before the next group's copies overwrite them
         }
         if (active) {
-            if constexpr (mode_pdf(MODE)) {
-                float p = validA ? woz * kInvPiF : 0.0f;
-                if (a.opts.sampling && validA && known) p = (float)fast::table_pdf(m, in, fast::normalize_f32(wox, woy, woz), woz, a.opts.sampling);
-                a.out_pdf[i] = p;
-            }
+            if constexpr (mode_pdf(MODE))
+                a.out_pdf[i] = wo_pdf(m, a.opts.sampling, validA && known, lambert_pdf(validA, woz), in, wox, woy, woz);
             if constexpr (HAS_SAMPLE) {
                 const float wo2[3] = { validB ? sx : 0.0f, validB ? sy : 0.0f, validB ? sz : 0.0f };
                 store3(a.out_wo, i, wo2);
@@ -265,15 +254,7 @@ __global__ __launch_bounds__(kNchBlock) void k_table_nch_wide(BatchArgs a, int n
         const size_t span = (n_items - base < 64 ? n_items - base : 64) * (size_t)n_ch;   // floats this wave owns per output array
 
         MaterialDev m;
-        bool known = true;
-        if constexpr (MULTI) {
-            const int id = a.mat[i];
-            known = id >= 0 && id < a.n_materials;
-            m = a.materials[known ? id : 0];
-            known = known && m.kind == KIND_TABLE_NCH && m.n_ch == n_ch;
-        } else {
-            m = a.single;
-        }
+        const bool known = nch_material<MULTI>(a, i, n_ch, m);
         const float4 *texels = known ? m.texels : (const float4 *)a.materials;
         const int n_th = known ? m.n_th : 1, n_td = known ? m.n_td : 1, n_pd = known ? m.n_pd : 1;
 
@@ -329,8 +310,7 @@ __global__ __launch_bounds__(kNchBlock) void k_table_nch_wide(BatchArgs a, int n
             const double c = (double)fast::cos_or_nan32(wix + wiy + wiz, wox, woy, woz, a.opts.cosine != 0);
             lookup(fast::dir_f32(wox, woy, woz), valid, c, 1.0f, a.out_rgb);
             if constexpr (mode_pdf(MODE)) {
-                float p = valid ? woz * kInvPiF : 0.0f;
-                if (a.opts.sampling && valid && known) p = (float)fast::table_pdf(m, in, fast::normalize_f32(wox, woy, woz), woz, a.opts.sampling);
+                const float p = wo_pdf(m, a.opts.sampling, valid && known, lambert_pdf(valid, woz), in, wox, woy, woz);
                 if (active) a.out_pdf[i] = p;
             }
         }
@@ -374,9 +354,7 @@ __global__ __launch_bounds__(kNchBlock) void k_build_bricks_nch(const double *pl
         float v[8 * CPAD];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int sh = min(ih + (k >> 2), n_th - 1), sd = min(id + ((k >> 1) & 1), n_td - 1),
-                      sp = phi_periodic ? (ip + (k & 1)) % n_pd : min(ip + (k & 1), n_pd - 1);
-            const size_t src = ((size_t)sh * n_td + sd) * n_pd + sp;
+            const size_t src = brick_corner(ih, id, ip, k, n_th, n_td, n_pd, phi_periodic);
 #pragma unroll
             for (int ch = 0; ch < CPAD; ++ch) {
                 const int cidx = (CPAD == 4 ? 4 * g : 0) + ch;
@@ -419,8 +397,7 @@ hipError_t launch_nch_mode(const BatchArgs &a, bool multi, bool indexed, int n_c
     if constexpr (MODE == MODE_PDF) {
         return hipErrorInvalidValue;                           // the RGB pdf kernel serves n-channel tables
     } else {
-        if (indexed) return multi ? launch_nch_cpad<MODE, true, true>(a, n_ch, compute_units, stream) : launch_nch_cpad<MODE, false, true>(a, n_ch, compute_units, stream);
-        return multi ? launch_nch_cpad<MODE, true, false>(a, n_ch, compute_units, stream) : launch_nch_cpad<MODE, false, false>(a, n_ch, compute_units, stream);
+        return with_flags([&](auto multi_c, auto indexed_c) { return launch_nch_cpad<MODE, multi_c, indexed_c>(a, n_ch, compute_units, stream); }, multi, indexed);
     }
 }
 

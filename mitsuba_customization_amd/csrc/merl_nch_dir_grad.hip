@@ -75,12 +75,12 @@ hipError_t launch_table_grad_dir_nch(const BatchArgs &a, const DirGradOut &o, in
     if (n_ch < 1 || n_ch > kMaxChannels || n_ch == 3) return hipErrorInvalidValue;
     const int cpad = n_ch == 1 ? 1 : n_ch == 2 ? 2 : 4;
     const dim3 grid(grid_blocks(a.n, kNchDirBlock, (size_t)std::max(compute_units, 1) * nch_dir_blocks_per_cu(cpad))), block(kNchDirBlock);
-    dispatch_ids_queue(a, [&](auto per_lane, auto indexed) {
-        constexpr bool P = decltype(per_lane)::value, I = decltype(indexed)::value;
+    with_flags([&](auto per_lane, auto indexed) {
+        constexpr bool P = per_lane, I = indexed;
         if (cpad == 1) hipLaunchKernelGGL((k_table_grad_dir_nch<P, I, 1>), grid, block, 0, stream, a, o, n_ch, no_table);
         else if (cpad == 2) hipLaunchKernelGGL((k_table_grad_dir_nch<P, I, 2>), grid, block, 0, stream, a, o, n_ch, no_table);
         else hipLaunchKernelGGL((k_table_grad_dir_nch<P, I, 4>), grid, block, 0, stream, a, o, n_ch, no_table);
-    });
+    }, a.mat != nullptr, a.idx != nullptr);
     return hipGetLastError();
 }
 

@@ -284,8 +284,7 @@ template <int MODE, bool INDEXED, bool MULTI, int MASK = 0>
 __global__ __launch_bounds__(kRglBlock, rgl_min_blocks(MODE, MULTI, MASK)) void k_rgl(BatchArgs a, RglDev r)
 {
     const size_t stride = (size_t)gridDim.x * kRglBlock;
-    size_t n_items = a.n;
-    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; n_items = c < a.n ? c : a.n; }
+    const size_t n_items = item_count<INDEXED>(a);
     GridLds grids{ 0u, 0u };
     if constexpr (!MULTI) {
         unsigned at = 0;
@@ -317,8 +316,7 @@ __global__ __launch_bounds__(rgl_lds_block(MODE, MASK)) void k_rgl_lds(BatchArgs
 {
     constexpr int kRglLdsBlock = rgl_lds_block(MODE, MASK);
     const size_t stride = (size_t)gridDim.x * kRglLdsBlock;
-    size_t n_items = a.n;
-    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; n_items = c < a.n ? c : a.n; }
+    const size_t n_items = item_count<INDEXED>(a);
     unsigned at = 0;
     const GridLds grids = stage_grids(r, at, kRglLdsBlock);
     if constexpr (MARG_ONLY) {
@@ -442,6 +440,15 @@ int lds_limit()
     return limit;
 }
 
+// a launch whose kernel keeps tables in dynamic LDS: raises the kernel's limit to `lds` bytes first
+template <class... P>
+hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, P... args)
+{
+    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
 template <int MODE, int MASK>
 hipError_t launch_masked(const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream)
 {
@@ -455,35 +462,23 @@ hipError_t launch_masked(const BatchArgs &a, const RglDev *r, bool indexed, int 
         const size_t need = lds_bytes_of(*r), need_marg = lds_marg_bytes_of(*r);
         if (need <= (size_t)lds_limit()) {
             constexpr int kThreads = rgl_lds_block(MODE, kLdsMask);
-            if (indexed) {
-                (void)hipFuncSetAttribute((const void *)k_rgl_lds<MODE, true, false, kLdsMask>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-                hipLaunchKernelGGL((k_rgl_lds<MODE, true, false, kLdsMask>), grid_of(kThreads), dim3(kThreads), need, stream, a, *r);
-            } else {
-                (void)hipFuncSetAttribute((const void *)k_rgl_lds<MODE, false, false, kLdsMask>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-                hipLaunchKernelGGL((k_rgl_lds<MODE, false, false, kLdsMask>), grid_of(kThreads), dim3(kThreads), need, stream, a, *r);
-            }
-            return hipGetLastError();
+            return with_flags([&](auto ix) { return launch_with_lds(k_rgl_lds<MODE, ix, false, kLdsMask>, grid_of(kThreads), dim3(kThreads), need, stream, a, *r); },
+                              indexed);
         }
         // the marginal rows alone — sample() alone: eval / pdf read one marginal value per unit (not worth a copy per CU), and the fused
         // unit of such a file is issued as two launches (launch_rgl)
         if constexpr (MODE == MODE_SAMPLE) {
             if (need_marg <= (size_t)lds_limit()) {
                 constexpr int kThreads = rgl_lds_block(MODE, kMargMask);
-                if (indexed) {
-                    (void)hipFuncSetAttribute((const void *)k_rgl_lds<MODE, true, true, kMargMask>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need_marg);
-                    hipLaunchKernelGGL((k_rgl_lds<MODE, true, true, kMargMask>), grid_of(kThreads), dim3(kThreads), need_marg, stream, a, *r);
-                } else {
-                    (void)hipFuncSetAttribute((const void *)k_rgl_lds<MODE, false, true, kMargMask>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need_marg);
-                    hipLaunchKernelGGL((k_rgl_lds<MODE, false, true, kMargMask>), grid_of(kThreads), dim3(kThreads), need_marg, stream, a, *r);
-                }
-                return hipGetLastError();
+                return with_flags([&](auto ix) {
+                    return launch_with_lds(k_rgl_lds<MODE, ix, true, kMargMask>, grid_of(kThreads), dim3(kThreads), need_marg, stream, a, *r);
+                }, indexed);
             }
         }
     }
     const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
     const size_t grids = grid_bytes_of(*r);                     // (at most 32 KB: 4,096 nodes per grid)
-    if (indexed) hipLaunchKernelGGL((k_rgl<MODE, true, false, MASK>), grid, block, grids, stream, a, *r);
-    else hipLaunchKernelGGL((k_rgl<MODE, false, false, MASK>), grid, block, grids, stream, a, *r);
+    with_flags([&](auto ix) { hipLaunchKernelGGL((k_rgl<MODE, ix, false, MASK>), grid, block, grids, stream, a, *r); }, indexed);
     return hipGetLastError();
 }
 
@@ -493,8 +488,7 @@ hipError_t launch_mode(const BatchArgs &a, const RglDev *r, bool indexed, int se
     if (!r) {                                                   // a batch with material ids: descriptors come from the material array
         const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
         const RglDev none{};
-        if (indexed) hipLaunchKernelGGL((k_rgl<MODE, true, true>), grid, block, 0, stream, a, none);
-        else hipLaunchKernelGGL((k_rgl<MODE, false, true>), grid, block, 0, stream, a, none);
+        with_flags([&](auto ix) { hipLaunchKernelGGL((k_rgl<MODE, ix, true>), grid, block, 0, stream, a, none); }, indexed);
         return hipGetLastError();
     }
     if (r->n_phi == 1 && r->n_theta > 1) return launch_masked<MODE, 5>(a, r, indexed, search, compute_units, stream);
@@ -698,9 +692,7 @@ hipError_t launch_spectral_masked(const BatchArgs &a, const RglDev &r, const flo
         const size_t need = lds_bytes_of(r);
         if (need <= (size_t)lds_limit()) {
             constexpr int kThreads = rgl_lds_block(MODE);
-            (void)hipFuncSetAttribute((const void *)k_rgl_spectral<MODE, true, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            hipLaunchKernelGGL((k_rgl_spectral<MODE, true, MASK>), dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream, a, r, wl, W);
-            return hipGetLastError();
+            return launch_with_lds(k_rgl_spectral<MODE, true, MASK>, dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream, a, r, wl, W);
         }
     }
     hipLaunchKernelGGL((k_rgl_spectral<MODE, false, MASK>), dim3(rgl_grid(a.n, compute_units)), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
@@ -722,10 +714,8 @@ hipError_t launch_spectral_queue_masked(const BatchArgs &a, const RglDev &r, con
         const size_t need = lds_bytes_of(r);
         if (need <= (size_t)lds_limit()) {
             constexpr int kThreads = rgl_lds_block(MODE);
-            (void)hipFuncSetAttribute((const void *)k_rgl_spectral_q<MODE, true, false, true, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, false, true, MASK>), dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream,
-                               a, r, wl, W);
-            return hipGetLastError();
+            return launch_with_lds(k_rgl_spectral_q<MODE, true, false, true, MASK>, dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream,
+                                   a, r, wl, W);
         }
     }
     hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, false, false, MASK>), dim3(rgl_grid(a.n, compute_units)), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
@@ -737,8 +727,7 @@ hipError_t launch_spectral_queue_mode(const BatchArgs &a, const RglDev *r, bool 
     if (!r) {                                                   // material ids: descriptors come from the material array
         const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
         const RglDev none{};
-        if (indexed) hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, true, false>), grid, block, 0, stream, a, none, wl, W);
-        else hipLaunchKernelGGL((k_rgl_spectral_q<MODE, false, true, false>), grid, block, 0, stream, a, none, wl, W);
+        with_flags([&](auto ix) { hipLaunchKernelGGL((k_rgl_spectral_q<MODE, ix, true, false>), grid, block, 0, stream, a, none, wl, W); }, indexed);
         return hipGetLastError();
     }
     if (!indexed) return launch_spectral_mode<MODE>(a, *r, wl, W, search, compute_units, stream);

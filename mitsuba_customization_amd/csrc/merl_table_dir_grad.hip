@@ -60,11 +60,9 @@ __global__ __launch_bounds__(kTableDirBlock, kTableDirBlocksPerCu) void k_table_
 hipError_t launch_table_grad_dir(const BatchArgs &a, const DirGradOut &o, int layout, int compute_units, hipStream_t stream)
 {
     const dim3 grid(grid_blocks(a.n, kTableDirBlock, (size_t)std::max(compute_units, 1) * kTableDirBlocksPerCu)), block(kTableDirBlock);
-    dispatch_ids_queue(a, [&](auto per_lane, auto indexed) {
-        constexpr bool P = decltype(per_lane)::value, I = decltype(indexed)::value;
-        if (layout == LAYOUT_BRICK) hipLaunchKernelGGL((k_table_grad_dir<P, I, LAYOUT_BRICK>), grid, block, 0, stream, a, o);
-        else hipLaunchKernelGGL((k_table_grad_dir<P, I, LAYOUT_ROWS>), grid, block, 0, stream, a, o);
-    });
+    with_flags([&](auto per_lane, auto indexed, auto brick) {
+        hipLaunchKernelGGL((k_table_grad_dir<per_lane, indexed, brick ? LAYOUT_BRICK : LAYOUT_ROWS>), grid, block, 0, stream, a, o);
+    }, a.mat != nullptr, a.idx != nullptr, layout == LAYOUT_BRICK);
     return hipGetLastError();
 }
 

@@ -224,13 +224,11 @@ hipError_t launch_table_grad(GradArgs a, int variant, int compute_units, hipStre
     if (a.n == 0) return hipSuccess;
     const dim3 grid(grad_grid(a.n, compute_units)), block(kBlock);
     if (variant == 1) {
-        if (a.opts.lookup) hipLaunchKernelGGL(k_grad_naive<1>, grid, block, 0, stream, a);
-        else hipLaunchKernelGGL(k_grad_naive<0>, grid, block, 0, stream, a);
+        with_flags([&](auto trilinear) { hipLaunchKernelGGL(k_grad_naive<trilinear ? 1 : 0>, grid, block, 0, stream, a); }, a.opts.lookup != 0);
         return hipGetLastError();
     }
     a.merge = variant == 2 ? 1 : (variant == 3 ? 2 : 0);
-    if (a.opts.lookup) hipLaunchKernelGGL(k_grad_bricks<1>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(k_grad_bricks<0>, grid, block, 0, stream, a);
+    with_flags([&](auto trilinear) { hipLaunchKernelGGL(k_grad_bricks<trilinear ? 1 : 0>, grid, block, 0, stream, a); }, a.opts.lookup != 0);
     return hipGetLastError();
 }
 
