@@ -165,19 +165,92 @@ MRL_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v
 struct Rgbd { double r, g, b; };
 struct Rgbf { float r, g, b; };       // a looked-up BRDF value: Float, like the texels it is blended from
 
-// The 8 trilinear corner weights, formed in f64 from the f64 fractions (a fraction near 1 would lose its complement's
-// relative accuracy in Float) and rounded ONCE to Float; corner k = 4 a + 2 b + c along (axis 0, axis 1, azimuth).
-struct CornerWeights { float w[8]; };
-MRL_HD CornerWeights corner_weights(double fh, double fd, double fp)
+// Both splits take x in [-1, n] (every coordinate map of this file lands there: angles are atan2 results scaled by n / range,
+// minus the half-texel shift of the centre-node convention) or NaN, and stay inside the table for anything else.
+// clamped axis: i0 in [0,n-1], f in [0,1]; i0+1 is always a valid (padded) index.  (int)x truncates towards zero, which for
+// x > -1 is floor(x) clamped at 0 (v_cvt_i32_f64 saturates and maps NaN to 0): no floor, no lower clamp.
+// (contraction off in everything between a continuous coordinate and its Float corner weights: fused with the multiply
+// that produced x in one inlining context and not in another, x - i differs by ~1e-14, and the weights' rounding to
+// Float turns that into a one-ulp difference between entry points for about one unit in a million)
+MRL_HD void split_clamped(double x, int n, int &i0, double &f)
+{
+#pragma clang fp contract(off)
+    int i = min_i(trunc_i(x), n - 1);
+#if !defined(__HIP_DEVICE_COMPILE__)
+    i = i < 0 ? 0 : i;                         // x <= -1 only happens for masked garbage; the device's (x > -1) never needs it
+#endif
+    f = __builtin_fmin(__builtin_fmax(x - (double)i, 0.0), 1.0);
+    i0 = i;
+}
+// periodic axis: i0 in [0,n-1]; i0+1 <= n hits the appended wrap texel.  floor(x) is in [-1, n]: shifted by n it lies in
+// [n-1, 2n] and two unsigned min(j, j - n) steps bring it to [0, n-1] (j < n: j - n wraps around to a huge value and j wins).
+MRL_HD void split_periodic(double x, int n, int &i0, double &f)
+{
+#pragma clang fp contract(off)
+    const double fl = floor(x);
+    f = x - fl;
+    unsigned j = (unsigned)trunc_i(fl) + (unsigned)n;
+    j = min_u(j, j - (unsigned)n);
+    j = min_u(j, j - (unsigned)n);
+    i0 = (int)min_u(j, (unsigned)(n - 1));          // only reached by x outside [-1, n]: stay inside the table
+}
+
+// the azimuth axis: periodic, except for the mirrored standard form (0 and pi are its two ends)
+MRL_HD void split_phi(bool periodic, double x, int n, int &i0, double &f)
+{
+    int ip, ic; double fp, fc;
+    split_periodic(x, n, ip, fp);
+    split_clamped(x, n, ic, fc);
+    i0 = periodic ? ip : ic;
+    f = periodic ? fp : fc;
+}
+
+// The cell a lookup reads and the fractions inside it: the ONE place where table coordinates become a cell.  eval, the table adjoint
+// (merl_table_grad.hip) and the direction gradients (merl_table_dir_grad.hpp) are about the same cell because they all call these.
+struct TableCell { int h0, d0, p0; double fh, fd, fp; };
+
+// trilinear: the centre-node shift, both polar axes clamped, the azimuth as the parameterisation param (PARAM_*) has it.
+// PERIODIC_ONLY: every table of the caller is periodic in the azimuth (the half / diff form) — split_periodic directly, param is not read
+template <bool PERIODIC_ONLY = false>
+MRL_HD TableCell trilinear_cell(const Coords &c, int n_th, int n_td, int n_pd, int node, int param)
+{
+#pragma clang fp contract(off)
+    const double shift = node ? 0.5 : 0.0;
+    TableCell t;
+    split_clamped(c.xh - shift, n_th, t.h0, t.fh);
+    split_clamped(c.xd - shift, n_td, t.d0, t.fd);
+    if constexpr (PERIODIC_ONLY) split_periodic(c.xp - shift, n_pd, t.p0, t.fp);
+    else split_phi(param_phi_periodic(param), c.xp - shift, n_pd, t.p0, t.fp);
+    return t;
+}
+// nearest: the texel the unshifted coordinates fall into, no fractions — through the weights below that is all weight on corner 0
+MRL_HD TableCell nearest_cell(const Coords &c, int n_th, int n_td, int n_pd)
+{
+    return { clampi(trunc_i(c.xh), 0, n_th - 1), clampi(trunc_i(c.xd), 0, n_td - 1), clampi(trunc_i(c.xp), 0, n_pd - 1), 0.0, 0.0, 0.0 };
+}
+// the cell's index in [n_th][n_td][n_pd] order, in the integer type the caller addresses with (a table has at most 2^28 cells)
+template <class I = size_t>
+MRL_HD I cell_index(const TableCell &t, int n_td, int n_pd) { return ((I)t.h0 * n_td + t.d0) * n_pd + t.p0; }
+
+// The 8 trilinear corner weights: f64 products of the f64 fractions, corner k = 4 a + 2 b + c along (axis 0, axis 1, azimuth), each
+// stored as T.  Zero fractions (nearest_cell) give exactly 1 on corner 0 and 0 elsewhere.
+template <class T> struct CellWeightsT { T w[8]; };
+template <class T>
+MRL_HD CellWeightsT<T> cell_weights(double fh, double fd, double fp)
 {
 #pragma clang fp contract(off)
     const double gh = 1.0 - fh, gd = 1.0 - fd, gp = 1.0 - fp;
     const double a00 = gh * gd, a01 = gh * fd, a10 = fh * gd, a11 = fh * fd;
-    CornerWeights c;
-    c.w[0] = (float)(a00 * gp); c.w[1] = (float)(a00 * fp); c.w[2] = (float)(a01 * gp); c.w[3] = (float)(a01 * fp);
-    c.w[4] = (float)(a10 * gp); c.w[5] = (float)(a10 * fp); c.w[6] = (float)(a11 * gp); c.w[7] = (float)(a11 * fp);
+    CellWeightsT<T> c;
+    c.w[0] = (T)(a00 * gp); c.w[1] = (T)(a00 * fp); c.w[2] = (T)(a01 * gp); c.w[3] = (T)(a01 * fp);
+    c.w[4] = (T)(a10 * gp); c.w[5] = (T)(a10 * fp); c.w[6] = (T)(a11 * gp); c.w[7] = (T)(a11 * fp);
     return c;
 }
+// the RGB blend's: rounded ONCE to Float (formed in Float, a fraction near 1 would lose its complement's relative accuracy); the
+// n-channel blend's: the f64 products as they are
+using CornerWeights = CellWeightsT<float>;
+using CellWeights = CellWeightsT<double>;
+MRL_HD CornerWeights corner_weights(double fh, double fd, double fp) { return cell_weights<float>(fh, fd, fp); }
 
 // Blend of one 96-B brick (8 corners x RGB f32, corner-major: float 3 k + ch) in packed Float math.  The brick's 24
 // floats are 12 aligned register pairs that cycle through (r,g) (b,r) (g,b): three pair accumulators A, B, C take four
@@ -244,88 +317,49 @@ MRL_HD Rgbf blend_brick_as(int blend, const float4 &q0, const float4 &q1, const 
     return blend_brick(q0, q1, q2, q3, q4, q5, c);
 }
 
+// The cell's 24 floats in brick order (corner-major RGB: float 3 k + ch) as six float4, all loads issued before any use.  A brick IS
+// that, one 128-B line, six 16-B loads; the rows layout gathers its eight texels and repacks them, so that a rows-layout table, a
+// brick table and the host image of either go through the same blend and give the same bits for the same coordinates
+template <int LAYOUT>
+MRL_HD const float4 *cell_texel(const MaterialDev &m, const TableCell &t)
+{
+    if constexpr (LAYOUT == LAYOUT_BRICK) return m.texels + cell_index(t, m.n_td, m.n_pd) * 8;     // corner 0 = the texel itself
+    else return m.texels + ((size_t)t.h0 * m.row_th + (size_t)t.d0 * m.row_td + t.p0);
+}
+template <int LAYOUT>
+MRL_HD void load_cell(const MaterialDev &m, const TableCell &t, float4 q[6])
+{
+    const float4 *b = cell_texel<LAYOUT>(m, t);
+    if constexpr (LAYOUT == LAYOUT_BRICK) {
+        q[0] = b[0]; q[1] = b[1]; q[2] = b[2]; q[3] = b[3]; q[4] = b[4]; q[5] = b[5];
+    } else {
+        const float4 t000 = b[0],                 t001 = b[1];
+        const float4 t010 = b[m.row_td],          t011 = b[m.row_td + 1];
+        const float4 t100 = b[m.row_th],          t101 = b[m.row_th + 1];
+        const float4 t110 = b[m.row_th + m.row_td], t111 = b[m.row_th + m.row_td + 1];
+        q[0] = make_float4(t000.x, t000.y, t000.z, t001.x); q[1] = make_float4(t001.y, t001.z, t010.x, t010.y);
+        q[2] = make_float4(t010.z, t011.x, t011.y, t011.z); q[3] = make_float4(t100.x, t100.y, t100.z, t101.x);
+        q[4] = make_float4(t101.y, t101.z, t110.x, t110.y); q[5] = make_float4(t110.z, t111.x, t111.y, t111.z);
+    }
+}
+
 // blend: BLEND_STORED returns the texel as stored; the other two policies have nothing to blend and return it clamped at 0
 template <int LAYOUT>
 MRL_HD Rgbf lookup_nearest_t(const MaterialDev &m, const Coords &c, int blend = BLEND_STORED)
 {
-    int ih = clampi(trunc_i(c.xh), 0, m.n_th - 1);
-    int id = clampi(trunc_i(c.xd), 0, m.n_td - 1);
-    int ip = clampi(trunc_i(c.xp), 0, m.n_pd - 1);
-    float4 t;
-    if constexpr (LAYOUT == LAYOUT_BRICK) t = m.texels[(((size_t)ih * m.n_td + id) * m.n_pd + ip) * 8];     // corner 0 = the texel itself
-    else t = m.texels[(size_t)ih * m.row_th + (size_t)id * m.row_td + ip];
+    float4 t = *cell_texel<LAYOUT>(m, nearest_cell(c, m.n_th, m.n_td, m.n_pd));
     if (blend != BLEND_STORED) t = max0(t);
     return { t.x, t.y, t.z };
 }
 
-// Both splits take x in [-1, n] (every coordinate map of this file lands there: angles are atan2 results scaled by n / range,
-// minus the half-texel shift of the centre-node convention) or NaN, and stay inside the table for anything else.
-// clamped axis: i0 in [0,n-1], f in [0,1]; i0+1 is always a valid (padded) index.  (int)x truncates towards zero, which for
-// x > -1 is floor(x) clamped at 0 (v_cvt_i32_f64 saturates and maps NaN to 0): no floor, no lower clamp.
-// (contraction off in everything between a continuous coordinate and its Float corner weights: fused with the multiply
-// that produced x in one inlining context and not in another, x - i differs by ~1e-14, and the weights' rounding to
-// Float turns that into a one-ulp difference between entry points for about one unit in a million)
-MRL_HD void split_clamped(double x, int n, int &i0, double &f)
-{
-#pragma clang fp contract(off)
-    int i = min_i(trunc_i(x), n - 1);
-#if !defined(__HIP_DEVICE_COMPILE__)
-    i = i < 0 ? 0 : i;                         // x <= -1 only happens for masked garbage; the device's (x > -1) never needs it
-#endif
-    f = __builtin_fmin(__builtin_fmax(x - (double)i, 0.0), 1.0);
-    i0 = i;
-}
-// periodic axis: i0 in [0,n-1]; i0+1 <= n hits the appended wrap texel.  floor(x) is in [-1, n]: shifted by n it lies in
-// [n-1, 2n] and two unsigned min(j, j - n) steps bring it to [0, n-1] (j < n: j - n wraps around to a huge value and j wins).
-MRL_HD void split_periodic(double x, int n, int &i0, double &f)
-{
-#pragma clang fp contract(off)
-    const double fl = floor(x);
-    f = x - fl;
-    unsigned j = (unsigned)trunc_i(fl) + (unsigned)n;
-    j = min_u(j, j - (unsigned)n);
-    j = min_u(j, j - (unsigned)n);
-    i0 = (int)min_u(j, (unsigned)(n - 1));          // only reached by x outside [-1, n]: stay inside the table
-}
-
-// the azimuth axis: periodic, except for the mirrored standard form (0 and pi are its two ends)
-MRL_HD void split_phi(bool periodic, double x, int n, int &i0, double &f)
-{
-    int ip, ic; double fp, fc;
-    split_periodic(x, n, ip, fp);
-    split_clamped(x, n, ic, fc);
-    i0 = periodic ? ip : ic;
-    f = periodic ? fp : fc;
-}
-
+// the same blend as k_table_dma's (entry points agree bit for bit)
 template <int LAYOUT>
 MRL_HD Rgbf lookup_trilinear_t(const MaterialDev &m, const Coords &c, int node, int blend = BLEND_STORED)
 {
-#pragma clang fp contract(off)
-    const double shift = node ? 0.5 : 0.0;
-    int h0, d0, p0; double fh, fd, fp;
-    split_clamped(c.xh - shift, m.n_th, h0, fh);
-    split_clamped(c.xd - shift, m.n_td, d0, fd);
-    split_phi(param_phi_periodic(m.param), c.xp - shift, m.n_pd, p0, fp);
-    if constexpr (LAYOUT == LAYOUT_BRICK) {
-        // one 128-B line holds the whole neighbourhood: 8 corners x RGB f32 = 96 B, six 16-B loads; the same blend as
-        // k_table_dma's (entry points agree bit for bit)
-        const float4 *q = m.texels + (((size_t)h0 * m.n_td + d0) * m.n_pd + p0) * 8;
-        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
-        return blend_brick_as(blend, q0, q1, q2, q3, q4, q5, corner_weights(fh, fd, fp));
-    }
-    const float4 *b = m.texels + ((size_t)h0 * m.row_th + (size_t)d0 * m.row_td + p0);
-    // issue all eight 16-B gathers before any use
-    const float4 t000 = b[0],                 t001 = b[1];
-    const float4 t010 = b[m.row_td],          t011 = b[m.row_td + 1];
-    const float4 t100 = b[m.row_th],          t101 = b[m.row_th + 1];
-    const float4 t110 = b[m.row_th + m.row_td], t111 = b[m.row_th + m.row_td + 1];
-    // the eight texels in brick order (corner-major RGB) through the SAME blend: a rows-layout table, a brick table and the
-    // host image of either give the same bits for the same coordinates
-    return blend_brick_as(blend, make_float4(t000.x, t000.y, t000.z, t001.x), make_float4(t001.y, t001.z, t010.x, t010.y),
-                          make_float4(t010.z, t011.x, t011.y, t011.z), make_float4(t100.x, t100.y, t100.z, t101.x),
-                          make_float4(t101.y, t101.z, t110.x, t110.y), make_float4(t110.z, t111.x, t111.y, t111.z),
-                          corner_weights(fh, fd, fp));
+    const TableCell t = trilinear_cell(c, m.n_th, m.n_td, m.n_pd, node, m.param);
+    float4 q[6];
+    load_cell<LAYOUT>(m, t, q);
+    return blend_brick_as(blend, q[0], q[1], q[2], q[3], q[4], q[5], corner_weights(t.fh, t.fd, t.fp));
 }
 
 // runtime-layout wrappers (generic kernel)

@@ -215,14 +215,9 @@ struct BrickWeights { double fh, fd, fp; };
 template <bool STD>
 __device__ __forceinline__ uint32_t brick_cell(const MaterialDev &m, const Coords &c, int node, BrickWeights &w)
 {
-#pragma clang fp contract(off)
-    const double shift = node ? 0.5 : 0.0;
-    int h0, d0, p0;
-    split_clamped(c.xh - shift, m.n_th, h0, w.fh);
-    split_clamped(c.xd - shift, m.n_td, d0, w.fd);
-    if constexpr (STD) split_phi(param_phi_periodic(m.param), c.xp - shift, m.n_pd, p0, w.fp);
-    else split_periodic(c.xp - shift, m.n_pd, p0, w.fp);
-    return (uint32_t)((h0 * m.n_td + d0) * m.n_pd + p0);
+    const TableCell t = trilinear_cell<!STD>(c, m.n_th, m.n_td, m.n_pd, node, m.param);
+    w = { t.fh, t.fd, t.fp };
+    return (uint32_t)cell_index<int>(t, m.n_td, m.n_pd);
 }
 
 // POLICY = false: the plain blend, no branch (the headline instantiation); true: MRL_OPT_NEGATIVE's policy (wave-uniform)

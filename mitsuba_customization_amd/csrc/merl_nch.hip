@@ -33,26 +33,18 @@ template <int S> __device__ __forceinline__ unsigned nch_swz(unsigned u)
     else return (u >> 3) & 1u;
 }
 
-struct NchWeights { double w[8]; };
+using NchWeights = CellWeights;        // the f64 corner weights as they are
 
 // a3 tail: cell index + the 8 corner weights.  Nearest lookups are the trilinear blend with all weight on corner 0.
+// trilinear_cell takes a parameterisation, not the flag, because of the compiler's output: with a flag that the caller evaluates,
+// k_table_dma<3, false, true, false, false, true> gains an s_nop, and the rule for single-material forward bodies is "the same count of
+// every opcode" (profiles/table_cell_shared_code_ab.txt).  The kernels here decide the azimuth's kind once per unit, before the maps
+// (with their param instead, 14 of their bodies move): the flag goes in as a parameterisation of that kind.
 __device__ __forceinline__ uint32_t nch_cell(int n_th, int n_td, int n_pd, bool phi_periodic, const Coords &c, const Options &o, NchWeights &out)
 {
-    int h0, d0, p0;
-    double fh, fd, fp;
-    if (o.lookup) {
-        const double shift = o.node ? 0.5 : 0.0;
-        split_clamped(c.xh - shift, n_th, h0, fh);
-        split_clamped(c.xd - shift, n_td, d0, fd);
-        split_phi(phi_periodic, c.xp - shift, n_pd, p0, fp);
-    } else {
-        h0 = clampi((int)c.xh, 0, n_th - 1); d0 = clampi((int)c.xd, 0, n_td - 1); p0 = clampi((int)c.xp, 0, n_pd - 1);
-        fh = fd = fp = 0.0;
-    }
-    const double gh = 1.0 - fh, gd = 1.0 - fd, gp = 1.0 - fp;
-    out.w[0] = gh * gd * gp; out.w[1] = gh * gd * fp; out.w[2] = gh * fd * gp; out.w[3] = gh * fd * fp;
-    out.w[4] = fh * gd * gp; out.w[5] = fh * gd * fp; out.w[6] = fh * fd * gp; out.w[7] = fh * fd * fp;
-    return (uint32_t)((h0 * n_td + d0) * n_pd + p0);
+    const TableCell t = o.lookup ? trilinear_cell(c, n_th, n_td, n_pd, o.node, phi_periodic ? PARAM_STANDARD_FULL : PARAM_STANDARD) : nearest_cell(c, n_th, n_td, n_pd);
+    out = cell_weights<double>(t.fh, t.fd, t.fp);
+    return (uint32_t)cell_index<int>(t, n_td, n_pd);
 }
 
 // cooperative copy of the wave's 64 bricks (S pieces each) into lds_slots[64 * S]; brick_addr = this lane's brick

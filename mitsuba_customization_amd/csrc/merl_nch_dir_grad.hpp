@@ -2,8 +2,8 @@
 // DESIGN.md §5k): the function k_table_grad_dir_nch runs, __host__ __device__ and free of HIP calls so that a host harness can run it.
 //
 // The operator and the math are those of merl_table_dir_grad.hpp with c running over n_ch channels: E_c = T_c(x(a, b)) kappa, T_c the
-// exact trilinear interpolant of the stored Float texels in the cell eval_nch selects (nch_cell of merl_nch.hip: the same split, shift
-// and clamps as the RGB path's, the periodic azimuth of the half / diff and full forms).  Step 1 walks the cell's channel groups:
+// exact trilinear interpolant of the stored Float texels in the cell eval_nch selects (trilinear_cell / nearest_cell of merl_device.hpp, which nch_cell of
+// merl_nch.hip and fast::dir_cell both call: the RGB path's split, shift and clamps).  Step 1 walks the cell's channel groups:
 //   t_k = sum_c g_c (f[k][c] - f[0][c]), k = 1 .. 7, each difference exact in f64 BEFORE it meets g;   base = sum_c g_c f[0][c],
 // both accumulated channel by channel in ascending channel order in ONE chain, t = g_0 d_0, then t = fma(g_c, d_c, t): for three
 // channels this is the RGB function's expression, and a channel whose g is 0 leaves the chain's value as it was — an RGB table embedded
@@ -73,7 +73,7 @@ MRL_HD TableDirGrad nch_eval_dir_grad(const MaterialDev &m, const Options &o, fl
 #pragma clang fp contract(off)
     const DirCell s = dir_cell(m, o, wix, wiy, wiz, wox, woy, woz);
     const int groups = CPAD == 4 ? (n_ch + 3) / 4 : 1;             // wave-uniform: n_ch is an argument of the call
-    const float4 *cell = m.texels + ((((size_t)s.h0 * m.n_td + s.d0) * m.n_pd + s.p0) * groups) * (2 * CPAD);
+    const float4 *cell = m.texels + (cell_index(s.cell, m.n_td, m.n_pd) * groups) * (2 * CPAD);
     NchGroup<CPAD> cur, next;
     nch_load_group<CPAD>(cell, g, 0, n_ch, cur);
     next = cur;

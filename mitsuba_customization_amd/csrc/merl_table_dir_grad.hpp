@@ -34,27 +34,6 @@ struct TableDirGrad { float wi[3], wo[3]; };
 // below this a singular measure (rho^2, |e|^2, px^2 + py^2, ...) counts as zero: its reciprocal stays finite
 constexpr double kSingular = 1e-280;
 
-// the 24 floats of the cell (h0, d0, p0): corner-major RGB, corner k = 4 a + 2 b + c along (axis 0, axis 1, azimuth) — all loads are
-// issued before any use
-template <int LAYOUT>
-MRL_HD void load_cell(const MaterialDev &m, int h0, int d0, int p0, float f[24])
-{
-    if constexpr (LAYOUT == LAYOUT_BRICK) {
-        const float4 *q = m.texels + (((size_t)h0 * m.n_td + d0) * m.n_pd + p0) * 8;
-        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
-        f[0] = q0.x; f[1] = q0.y; f[2] = q0.z; f[3] = q0.w; f[4] = q1.x; f[5] = q1.y; f[6] = q1.z; f[7] = q1.w;
-        f[8] = q2.x; f[9] = q2.y; f[10] = q2.z; f[11] = q2.w; f[12] = q3.x; f[13] = q3.y; f[14] = q3.z; f[15] = q3.w;
-        f[16] = q4.x; f[17] = q4.y; f[18] = q4.z; f[19] = q4.w; f[20] = q5.x; f[21] = q5.y; f[22] = q5.z; f[23] = q5.w;
-    } else {
-        const float4 *b = m.texels + ((size_t)h0 * m.row_th + (size_t)d0 * m.row_td + p0);
-        const float4 t0 = b[0], t1 = b[1], t2 = b[m.row_td], t3 = b[m.row_td + 1];
-        const float4 t4 = b[m.row_th], t5 = b[m.row_th + 1], t6 = b[m.row_th + m.row_td], t7 = b[m.row_th + m.row_td + 1];
-        f[0] = t0.x; f[1] = t0.y; f[2] = t0.z; f[3] = t1.x; f[4] = t1.y; f[5] = t1.z; f[6] = t2.x; f[7] = t2.y; f[8] = t2.z;
-        f[9] = t3.x; f[10] = t3.y; f[11] = t3.z; f[12] = t4.x; f[13] = t4.y; f[14] = t4.z; f[15] = t5.x; f[16] = t5.y; f[17] = t5.z;
-        f[18] = t6.x; f[19] = t6.y; f[20] = t6.z; f[21] = t7.x; f[22] = t7.y; f[23] = t7.z;
-    }
-}
-
 // (1 - t) u + t v
 MRL_HD double lerp_fma(double s, double t, double u, double v)
 {
@@ -152,9 +131,8 @@ struct DirCell {
     Vec3 a, b;
     double c_xh;                 // the unshifted first coordinate (the sqrt warp's derivative needs it)
     bool mh, md, mp;             // df / dx is 1: trilinear, and no lower clamp active on the shifted coordinate (the azimuth: or periodic)
-    double fh, fd, fp;
+    TableCell cell;              // the cell eval selects and its fractions (a dead unit's: some cell inside the table)
     double k_th, k_td, k_pd;
-    int h0, d0, p0;
     bool trilinear, periodic;
     float kappa;                 // eval_tail's Float wo.z (or 1; NaN when an input is not finite)
     bool live;                   // not one of eval's dead units
@@ -169,21 +147,16 @@ MRL_HD DirCell dir_cell(const MaterialDev &m, const Options &o, float wix, float
     s.a = unit(s.in_dir); s.b = unit(s.out_dir);
     const Coords c = maps(normalize_f32(wix, wiy, wiz), s.out_dir);         // eval's own coordinates: they select the cell
     s.trilinear = o.lookup != 0; s.periodic = param_phi_periodic(m.param);
-    const double shift = (s.trilinear && o.node) ? 0.5 : 0.0;
+    const int node = s.trilinear && o.node;
+    const double shift = node ? 0.5 : 0.0;
     s.c_xh = c.xh;
-    const double xh = c.xh - shift, xd = c.xd - shift, xp = c.xp - shift;
-    s.mh = s.trilinear && xh >= 0.0; s.md = s.trilinear && xd >= 0.0; s.mp = s.trilinear && (s.periodic || xp >= 0.0);
+    s.mh = s.trilinear && c.xh - shift >= 0.0; s.md = s.trilinear && c.xd - shift >= 0.0; s.mp = s.trilinear && (s.periodic || c.xp - shift >= 0.0);
     s.k_th = maps.k_th; s.k_td = maps.k_td; s.k_pd = maps.k_pd;
-    int h0, d0, p0;
-    double fh, fd, fp;
-    split_clamped(xh, m.n_th, h0, fh);
-    split_clamped(xd, m.n_td, d0, fd);
-    split_phi(s.periodic, xp, m.n_pd, p0, fp);
-    // a nearest lookup: lookup_nearest_t's cell, no fractions
-    h0 = s.trilinear ? h0 : trunc_i(c.xh); d0 = s.trilinear ? d0 : trunc_i(c.xd); p0 = s.trilinear ? p0 : trunc_i(c.xp);
-    s.fh = s.trilinear ? fh : 0.0; s.fd = s.trilinear ? fd : 0.0; s.fp = s.trilinear ? fp : 0.0;
-    // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table
-    s.h0 = clampi(h0, 0, m.n_th - 1); s.d0 = clampi(d0, 0, m.n_td - 1); s.p0 = clampi(p0, 0, m.n_pd - 1);
+    // eval's cell under either lookup, selected (the option is wave-uniform; a nearest lookup has no fractions).  A dead unit's
+    // coordinates are garbage: whatever they are, the trilinear cell stays inside the table (nearest_cell's already does)
+    TableCell tri = trilinear_cell(c, m.n_th, m.n_td, m.n_pd, node, m.param);
+    tri.h0 = clampi(tri.h0, 0, m.n_th - 1); tri.d0 = clampi(tri.d0, 0, m.n_td - 1); tri.p0 = clampi(tri.p0, 0, m.n_pd - 1);
+    s.cell = s.trilinear ? tri : nearest_cell(c, m.n_th, m.n_td, m.n_pd);
     s.kappa = cos_or_nan32((wix + wiy + wiz), wox, woy, woz, o.cosine != 0);
     s.live = (wiz > 0.0f) && (woz > 0.0f) && (s.kappa == s.kappa);
     return s;
@@ -196,7 +169,7 @@ struct DirForms { double V, Xh, Xd, Xp; };
 MRL_HD DirForms dir_forms(const DirCell &s, const double t[8], double base)
 {
 #pragma clang fp contract(off)
-    const double fh = s.fh, fd = s.fd, fp = s.fp;
+    const double fh = s.cell.fh, fd = s.cell.fd, fp = s.cell.fp;
     const double gh = 1.0 - fh, gd = 1.0 - fd, gp = 1.0 - fp;
     DirForms r;
     r.V = base + lerp_fma(gh, fh, lerp_fma(gd, fd, fp * t[1], lerp_fma(gp, fp, t[2], t[3])),
@@ -242,8 +215,11 @@ MRL_HD TableDirGrad table_eval_dir_grad(const MaterialDev &m, const Options &o, 
 {
 #pragma clang fp contract(off)
     const DirCell s = dir_cell(m, o, wix, wiy, wiz, wox, woy, woz);
+    float4 q[6];                                                 // lookup_trilinear_t's loads: corner-major RGB, float 3 k + ch
+    load_cell<LAYOUT>(m, s.cell, q);
     float f[24];
-    load_cell<LAYOUT>(m, s.h0, s.d0, s.p0, f);
+#pragma unroll
+    for (int p = 0; p < 6; ++p) { f[4 * p] = q[p].x; f[4 * p + 1] = q[p].y; f[4 * p + 2] = q[p].z; f[4 * p + 3] = q[p].w; }
 
     // 1. per channel the seven exact differences to corner 0, u_k[c] = f[k][c] - f[0][c], contracted with g: t_k = sum_c g_c u_k[c] (t_0 = 0).
     //    V is sum_c g_c f[0][c] plus the trilinear form of the t_k, the three D_axis the bilinear forms of their differences

@@ -33,10 +33,10 @@ struct GradArgs {
 // f64 add without a compare-and-swap loop (global_atomic_add_f64 / flat_atomic_add_f64); the destinations are device allocations
 __device__ __forceinline__ void add_f64(double *p, double v) { (void)unsafeAtomicAdd(p, v); }
 
-// What unit i adds: cell (h0, d0, p0) of its lookup (-1: eval masks the unit), the Float corner weights and, per channel,
-// scale x (cos(theta_o) or 1) x g in f64.  Masking is a select: a dead unit's g may be NaN.
+// What unit i adds: the cell of its lookup (eval's own TableCell, kept inside the table; the kernels read its indices only), whether
+// eval masks the unit, the Float corner weights and, per channel, scale x (cos(theta_o) or 1) x g in f64.  Masking is a select: a dead unit's g may be NaN.
 struct GradUnit {
-    int h0, d0, p0;
+    TableCell cell;
     bool live;
     float w[8];
     double s[3];
@@ -59,23 +59,15 @@ __device__ __forceinline__ GradUnit grad_unit(const GradArgs &a, const fast::Tab
     u.live = in_range && (wiz > 0.0f) && (woz > 0.0f) && (c32 == c32);
     const fast::Vec3 in = fast::normalize_f32(wix, wiy, wiz);
     const Coords c = maps(in, fast::dir_f32(wox, woy, woz));
+    // eval's own cell and weights (a nearest lookup: all weight on corner 0)
+    u.cell = LOOKUP ? trilinear_cell(c, a.n_th, a.n_td, a.n_pd, a.opts.node, a.param) : nearest_cell(c, a.n_th, a.n_td, a.n_pd);
+    const CornerWeights cw = corner_weights(u.cell.fh, u.cell.fd, u.cell.fp);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u.w[k] = u.live ? cw.w[k] : 0.0f;
+    // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table (nearest_cell's already does)
     if constexpr (LOOKUP) {
-        const double shift = a.opts.node ? 0.5 : 0.0;
-        double fh, fd, fp;
-        split_clamped(c.xh - shift, a.n_th, u.h0, fh);
-        split_clamped(c.xd - shift, a.n_td, u.d0, fd);
-        split_phi(param_phi_periodic(a.param), c.xp - shift, a.n_pd, u.p0, fp);
-        const CornerWeights cw = corner_weights(fh, fd, fp);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) u.w[k] = u.live ? cw.w[k] : 0.0f;
-    } else {
-        u.h0 = trunc_i(c.xh); u.d0 = trunc_i(c.xd); u.p0 = trunc_i(c.xp);
-        u.w[0] = u.live ? 1.0f : 0.0f;
-#pragma unroll
-        for (int k = 1; k < 8; ++k) u.w[k] = 0.0f;
+        u.cell.h0 = clampi(u.cell.h0, 0, a.n_th - 1); u.cell.d0 = clampi(u.cell.d0, 0, a.n_td - 1); u.cell.p0 = clampi(u.cell.p0, 0, a.n_pd - 1);
     }
-    // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table
-    u.h0 = clampi(u.h0, 0, a.n_th - 1); u.d0 = clampi(u.d0, 0, a.n_td - 1); u.p0 = clampi(u.p0, 0, a.n_pd - 1);
     const double cd = (double)c32;
     u.s[0] = u.live ? a.scale[0] * cd * (double)g0 : 0.0;
     u.s[1] = u.live ? a.scale[1] * cd * (double)g1 : 0.0;
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void k_grad_bricks(GradArgs a)
     for (size_t r = 0; r < rounds; ++r) {
         const size_t i = r * stride + (size_t)blockIdx.x * kBlock + t;
         const GradUnit u = grad_unit<LOOKUP>(a, maps, i);
-        const int cell = u.live ? (u.h0 * a.n_td + u.d0) * a.n_pd + u.p0 : -1;
+        const int cell = u.live ? cell_index<int>(u.cell, a.n_td, a.n_pd) : -1;
         s_cell[t] = cell;
 #pragma unroll
         for (int q = 0; q < (LOOKUP ? 8 : 1); ++q) s_w[q][t] = u.w[q];
@@ -202,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void k_grad_naive(GradArgs a)
         if (!u.live) continue;
 #pragma unroll
         for (int k = 0; k < (LOOKUP ? 8 : 1); ++k) {
-            int h = u.h0 + (k >> 2), d = u.d0 + ((k >> 1) & 1), p = u.p0 + (k & 1);
+            int h = u.cell.h0 + (k >> 2), d = u.cell.d0 + ((k >> 1) & 1), p = u.cell.p0 + (k & 1);
             h = h == a.n_th ? a.n_th - 1 : h;
             d = d == a.n_td ? a.n_td - 1 : d;
             p = p == a.n_pd ? (periodic ? 0 : a.n_pd - 1) : p;
