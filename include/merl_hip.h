@@ -489,6 +489,14 @@ typedef struct mrl_route_launch {
 } mrl_route_launch;
 size_t mrl_batch_route(int mode, int variant, int layout, int lookup, int negative, int any_standard, int material, int queued,
                        int has_ggx, int has_table, size_t n, mrl_route_launch *out, size_t max_out);
+/* The same for a call on an adaptive-parameterisation (RGL) material: the RGB calls when the material, or some material of a call
+ * with ids, is an RGL file (spectral 0; with ids this launch follows the table / GGX launch of mrl_batch_route), and the mrl_*_spectral_*
+ * calls (spectral 1; mode 1 names no spectral call).  ids: a material id per unit; search: MRL_OPT_RGL_SEARCH; n_phi, n_theta, nx, ny,
+ * n_wl: the one file's parameter grid, warp resolution and wavelength nodes (unused with ids); lds_limit: the device's LDS bytes per
+ * workgroup.  One launch, or two for the fused unit of a file whose running integrals exceed lds_limit (eval + pdf, then sample);
+ * whole_xcds is 0. */
+size_t mrl_rgl_route(int mode, int spectral, int ids, int queued, int search, size_t n, int n_phi, int n_theta, int nx, int ny, int n_wl,
+                     size_t lds_limit, mrl_route_launch *out, size_t max_out);
 
 /* ---- fitting tables: the adjoint of eval ----
  * With MRL_OPT_NEGATIVE at clamp or keep, eval of an RGB table material is linear in the uploaded planar array T: eval(T) = A T,

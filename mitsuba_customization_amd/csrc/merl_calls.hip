@@ -437,6 +437,18 @@ size_t mrl_batch_route(int mode, int variant, int layout, int lookup, int negati
     return count;
 }
 
+size_t mrl_rgl_route(int mode, int spectral, int ids, int queued, int search, size_t n, int n_phi, int n_theta, int nx, int ny, int n_wl,
+                     size_t lds_limit, mrl_route_launch *out, size_t max_out)
+{
+    const mrl::RglRoute route = mrl::route_rgl(mode, spectral != 0, ids != 0, queued != 0, search, n, { n_phi, n_theta, nx, ny, n_wl }, lds_limit);
+    for (size_t l = 0; out && l < (size_t)route.count && l < max_out; ++l) {
+        const mrl::RglChoice &k = route.launch[l];
+        std::snprintf(out[l].kernel, sizeof out[l].kernel, "%s", mrl::kernel_name(k).c_str());
+        out[l].block = k.block; out[l].blocks_per_cu = k.blocks_per_cu; out[l].whole_xcds = 0;
+    }
+    return (size_t)route.count;
+}
+
 int mrl_generate_pairs(mrl_ctx *ctx, uint64_t seed, uint64_t first_index, size_t n, float *wi, float *wo, float *u)
 {
     if (!ctx) return MRL_ERR_INVALID;

@@ -210,12 +210,36 @@ RglDev rgl_descriptor(const RglFields &f, const RglLayout &l, const float *base)
 // a CU's LDS, 1 = always from memory (the results are the same bits)
 hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, int search, int compute_units, hipStream_t stream);
 // a spectral RGL material: a.out_rgb / a.out_weight hold n x W values at the per-unit wavelengths wl [n][W] (nullptr: the file's own
-// wavelength nodes, W = their number); single material, whole arrays
-hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream);
-// the same over a queue (a.idx != nullptr: a.idx / a.idx_count, a.n = the capacity) and / or with a material id per unit (r == nullptr: a.mat,
-// a.materials; a unit whose id names no live spectral RGL material gets zeros in every output of the mode); any mode but MODE_PDF
+// wavelength nodes, W = their number) — whole arrays, over a queue (a.idx != nullptr: a.idx / a.idx_count, a.n = the capacity) and / or
+// with a material id per unit (r == nullptr: a.mat, a.materials; a unit whose id names no live spectral RGL material gets zeros in
+// every output of the mode); any mode but MODE_PDF
 hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, const float *wl, int W, int search, int compute_units,
                                  hipStream_t stream);
+// Which kernels serve those two entries, the way route_batch does it for the RGB tables: pure arithmetic, no HIP call (lds_limit: the
+// device's LDS per workgroup, an input).  Exported as mrl_rgl_route; tests/test_rgl_route_cpu.py restates the rules.
+enum RglFamily : int { KERNEL_RGL = 0, KERNEL_RGL_LDS = 1, KERNEL_RGL_SPECTRAL = 2, KERNEL_RGL_SPECTRAL_Q = 3 };
+// where a single-material kernel reads the distributions' running integrals: the cell records in memory, a copy in LDS, or the
+// marginal rows from LDS and the rest from memory
+enum RglTables : int { RGL_TABLES_MEM = 0, RGL_TABLES_LDS = 1, RGL_TABLES_LDS_MARG = 2 };
+struct RglShape { int n_phi, n_theta, nx, ny, n_wl; };      // of the launch's one file (material ids: unused)
+struct RglChoice {
+    int family, mode;
+    bool indexed;                    // INDEXED (k_rgl_spectral has no queue form: k_rgl_spectral_q serves its queues)
+    bool multi;                      // k_rgl, k_rgl_spectral_q: MULTI, the material comes from a.mat
+    int tables;                      // k_rgl_lds: MARG_ONLY = RGL_TABLES_LDS_MARG; k_rgl_spectral, k_rgl_spectral_q: LDS = RGL_TABLES_LDS
+    int mask;                        // MASK: 5 isotropic (n_phi == 1, n_theta > 1), 15 anisotropic (both > 1), 0 the shape is tested at run time
+    int block, blocks_per_cu;        // grid_blocks(n, block, compute units * blocks_per_cu): 1 for the kernels that copy tables into LDS, else 8
+    size_t lds_bytes;                // dynamic LDS: the parameter grids, and the tables by `tables`
+};
+struct RglRoute { int count; RglChoice launch[2]; };
+// multi: one launch of the memory kernel, mask 0.  One file, with copy = search == 0 && n >= 2^15 and fits = its integrals <= lds_limit:
+//   copy && fits                                        the LDS kernel, mask 5 or 0
+//   copy && !fits, RGB, MODE_EVAL_SAMPLE                two launches: MODE_EVAL_PDF then MODE_SAMPLE, each by these rules
+//   copy && !fits, RGB, MODE_SAMPLE, marginal rows fit  k_rgl_lds<2, ., true, 15 or 0>
+//   otherwise                                           the memory kernel, mask 5 / 15 / 0 (spectral: 5 / 0)
+// count 0: a value that names no mode, or MODE_PDF on a spectral file.
+RglRoute route_rgl(int mode, bool spectral, bool multi, bool indexed, int search, size_t n, const RglShape &s, size_t lds_limit);
+std::string kernel_name(const RglChoice &k);
 // ---- one-unit calls (merl_scalar.hip): a bounded-lifetime service kernel answers requests posted in pinned host memory ----
 struct ScalarBoard;
 struct ScalarArgs {

@@ -10,6 +10,9 @@
 //   k_rgl_spectral_q<MODE, INDEXED, MULTI, LDS, MASK>  spectral files over a wavefront queue (one material) or with a material id per unit
 // MASK: the bracket shape the kernel is compiled for (5 isotropic, 15 anisotropic, 0 tested at run time).  What bounds them — round
 // trips, then L1 line fills, then (isotropic) the vector ALU — and the measured rates: merl_rgl.hpp's header, DESIGN.md §5e.
+// The four are thin: each names its walk (rgl_walk: the launch's one material, grids and tables staged in LDS; rgl_walk_ids: a material
+// id per unit) and its unit (rgl_unit, rgl_unit_spectral).  Which of them a call launches is route_rgl (merl_kernels.hpp), pure
+// arithmetic exported as mrl_rgl_route and checked by tests/test_rgl_route_cpu.py; launch_route instantiates what it names.
 #include "merl_kernels.hpp"
 #include "merl_rgl.hpp"
 
@@ -40,9 +43,6 @@ constexpr int rgl_lds_block(int mode, int mask = 0)
     if (mode == MODE_EVAL_PDF && mask == 5) return MRL_RGL_LDS_BLOCK_EVALPDF5;
     return mode_sample(mode) || mode == MODE_EVAL_PDF ? (mask == 15 ? MRL_RGL_LDS_BLOCK_SAMPLE15 : MRL_RGL_LDS_BLOCK_SAMPLE) : MRL_RGL_LDS_BLOCK_EVAL;
 }
-// the grid-stride kernels (k_rgl, k_rgl_spectral without LDS): 8 blocks per CU
-inline unsigned rgl_grid(size_t n, int compute_units) { return grid_blocks(n, kRglBlock, (size_t)compute_units * 8); }
-
 // ---- the running integrals in LDS ----
 // Slice by slice (taken out of the records while they are copied: SearchLds below), for vndf and then luminance.  A ds_read gather of 64
 // scattered addresses costs no line fill, and these are the reads sample() is made of: 2 x (log2 ny + log2 nx) dependent steps per unit.
@@ -55,7 +55,7 @@ struct GridLds {
     __device__ __forceinline__ float theta_at(int k) const { return ((const float *)rgl_lds)[theta_at_ + (unsigned)k]; }
     __device__ __forceinline__ float wavelength_at(int k) const { return ((const float *)rgl_lds)[wl_at_ + (unsigned)k]; }
 };
-size_t grid_bytes_of(const RglDev &r) { return ((size_t)(r.n_phi + r.n_theta + r.n_wl) * sizeof(float) + 15) / 16 * 16; }
+size_t grid_bytes_of(const RglShape &r) { return ((size_t)(r.n_phi + r.n_theta + r.n_wl) * sizeof(float) + 15) / 16 * 16; }
 __device__ __forceinline__ GridLds stage_grids(const RglDev &r, unsigned &at_float4, int block)
 {
     float *g = (float *)rgl_lds;
@@ -150,11 +150,10 @@ struct SearchLdsMarg : rgl::SearchMem {
     __device__ __forceinline__ double marg(const rgl::Slices &s, int row) const { return marg_blend(s, marg_raw(s, row)); }
 };
 
-size_t lds_marg_bytes_of(const RglDev &r)
+size_t lds_marg_bytes_of(const RglShape &w)
 {
-    const WarpDev w = r.vndf();
     const size_t tb = w.n_theta > 1 ? w.n_theta - 1 : 1, pb = w.n_phi > 1 ? w.n_phi - 1 : 1;
-    return grid_bytes_of(r) + 2 * pb * tb * (size_t)(w.ny - 1) * sizeof(float4);
+    return grid_bytes_of(w) + 2 * pb * tb * (size_t)(w.ny - 1) * sizeof(float4);
 }
 
 __device__ __forceinline__ SearchLdsMarg stage_marg(const WarpDev &w, unsigned &at_float4, int block)
@@ -169,12 +168,11 @@ __device__ __forceinline__ SearchLdsMarg stage_marg(const WarpDev &w, unsigned &
 }
 
 // bytes of LDS the two distributions' running integrals take, slice by slice (16-B aligned pieces)
-size_t lds_bytes_of(const RglDev &r)
+size_t lds_bytes_of(const RglShape &w)
 {
-    const WarpDev w = r.vndf();
     const size_t slices = (size_t)w.n_phi * (size_t)w.n_theta, per_c = (size_t)(w.nx - 1) * (size_t)(w.ny - 1), per_r = (size_t)(w.ny - 1);
     const size_t left = (slices * per_c * 8 + 15) / 16 * 16, total = (slices * per_r * 8 + 15) / 16 * 16, marg = (slices * per_r * 4 + 15) / 16 * 16;
-    return grid_bytes_of(r) + 2 * (left + total + marg);
+    return grid_bytes_of(w) + 2 * (left + total + marg);
 }
 
 // one distribution's tables: memory (records, bracket-major) -> LDS (slice-major); every thread of the block takes part
@@ -280,32 +278,61 @@ constexpr int rgl_min_blocks(int mode, bool multi, int mask)
     return mode == MODE_EVAL_SAMPLE ? (multi ? MRL_RGL_MULTI_FUSED_BLOCKS : 2)
          : mode == MODE_SAMPLE ? MRL_RGL_SAMPLE_BLOCKS : mode == MODE_EVAL_PDF ? MRL_RGL_EVALPDF_BLOCKS : MRL_RGL_EVAL_BLOCKS;
 }
+// ---- the walk every RGL kernel makes: f(i) per lane, grid-stride, over the whole arrays or the queue (n_items: item_count) ----
+template <int BLOCK, bool INDEXED, class F>
+__device__ __forceinline__ void rgl_for_each(const BatchArgs &a, size_t n_items, F f)
+{
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    for (size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x; j < n_items; j += stride) f(INDEXED ? (size_t)a.idx[j] : j);
+}
+// The launch's one material: its parameter grids into LDS and, by TABLES (RglTables, merl_kernels.hpp), the distributions' running
+// integrals (RGL_TABLES_LDS), their marginal rows alone (RGL_TABLES_LDS_MARG: SearchLdsMarg) or nothing more; then unit(grids, tv, tl, i).
+template <int BLOCK, bool INDEXED, int TABLES, class Unit>
+__device__ __forceinline__ void rgl_walk(const BatchArgs &a, const RglDev &r, Unit unit)
+{
+    const size_t n_items = item_count<INDEXED>(a);
+    unsigned at = 0;
+    const GridLds grids = stage_grids(r, at, BLOCK);
+    auto walk = [&](const auto &tv, const auto &tl) {
+        __syncthreads();
+        rgl_for_each<BLOCK, INDEXED>(a, n_items, [&](size_t i) { unit(grids, tv, tl, i); });
+    };
+    if constexpr (TABLES == RGL_TABLES_LDS) {
+        const SearchLds tv = stage_search(r.vndf(), at, BLOCK);
+        const SearchLds tl = stage_search(r.luminance(), at, BLOCK);
+        walk(tv, tl);
+    } else if constexpr (TABLES == RGL_TABLES_LDS_MARG) {
+        const SearchLdsMarg tv = stage_marg(r.vndf(), at, BLOCK);
+        const SearchLdsMarg tl = stage_marg(r.luminance(), at, BLOCK);
+        walk(tv, tl);
+    } else {
+        walk(rgl::SearchMem(r.vndf()), rgl::SearchMem(r.luminance()));
+    }
+}
+// A material id per unit: unit(rm, grids, tv, tl, i) on the lanes whose id names a live material of KIND, through the descriptor stored
+// behind that material's image and its tables in memory; other(i) on every other lane.
+template <int BLOCK, bool INDEXED, int KIND, class Unit, class Other>
+__device__ __forceinline__ void rgl_walk_ids(const BatchArgs &a, Unit unit, Other other)
+{
+    rgl_for_each<BLOCK, INDEXED>(a, item_count<INDEXED>(a), [&](size_t i) {
+        const int id = a.mat[i];
+        if (id < 0 || id >= a.n_materials || a.materials[id].kind != KIND) { other(i); return; }
+        // the unit's descriptor into registers, whole (31 dwords read together): through a reference every table read would be
+        // two dependent loads — the pointer, then the data
+        const RglDev rm = *(const RglDev *)a.materials[id].rgl;
+        unit(rm, rgl::GridMem{ rm.phi, rm.theta, rm.wavelengths }, rgl::SearchMem(rm.vndf()), rgl::SearchMem(rm.luminance()), i);
+    });
+}
+
+// MULTI: the lanes whose id names no RGL material keep what the table / GGX kernel of the same call wrote
 template <int MODE, bool INDEXED, bool MULTI, int MASK = 0>
 __global__ __launch_bounds__(kRglBlock, rgl_min_blocks(MODE, MULTI, MASK)) void k_rgl(BatchArgs a, RglDev r)
 {
-    const size_t stride = (size_t)gridDim.x * kRglBlock;
-    const size_t n_items = item_count<INDEXED>(a);
-    GridLds grids{ 0u, 0u };
-    if constexpr (!MULTI) {
-        unsigned at = 0;
-        grids = stage_grids(r, at, kRglBlock);
-        __syncthreads();
-    }
-    for (size_t j = (size_t)blockIdx.x * kRglBlock + threadIdx.x; j < n_items; j += stride) {
-        const size_t i = INDEXED ? (size_t)a.idx[j] : j;
-        if constexpr (MULTI) {
-            const int id = a.mat[i];
-            if (id < 0 || id >= a.n_materials) continue;
-            const MaterialDev &m = a.materials[id];
-            if (m.kind != KIND_RGL) continue;
-            // the unit's descriptor into registers, whole (31 dwords read together): through a reference every table read would be
-            // two dependent loads — the pointer, then the data
-            const RglDev rm = *(const RglDev *)m.rgl;
-            rgl_unit<MODE, 0>(a, rm, rgl::GridMem{ rm.phi, rm.theta, rm.wavelengths }, rgl::SearchMem(rm.vndf()), rgl::SearchMem(rm.luminance()), i);
-        } else {
-            rgl_unit<MODE, MASK>(a, r, grids, rgl::SearchMem(r.vndf()), rgl::SearchMem(r.luminance()), i);
-        }
-    }
+    if constexpr (MULTI)
+        rgl_walk_ids<kRglBlock, INDEXED, KIND_RGL>(
+            a, [&](const RglDev &rm, const auto &g, const auto &tv, const auto &tl, size_t i) { rgl_unit<MODE, 0>(a, rm, g, tv, tl, i); }, [](size_t) {});
+    else
+        rgl_walk<kRglBlock, INDEXED, RGL_TABLES_MEM>(a, r, [&](const auto &g, const auto &tv, const auto &tl, size_t i) { rgl_unit<MODE, MASK>(a, r, g, tv, tl, i); });
 }
 
 // The single-material launch when the file's running integrals fit a CU's LDS: one workgroup per CU copies them in (once: the grid is
@@ -314,22 +341,8 @@ __global__ __launch_bounds__(kRglBlock, rgl_min_blocks(MODE, MULTI, MASK)) void 
 template <int MODE, bool INDEXED, bool MARG_ONLY = false, int MASK = 0>
 __global__ __launch_bounds__(rgl_lds_block(MODE, MASK)) void k_rgl_lds(BatchArgs a, RglDev r)
 {
-    constexpr int kRglLdsBlock = rgl_lds_block(MODE, MASK);
-    const size_t stride = (size_t)gridDim.x * kRglLdsBlock;
-    const size_t n_items = item_count<INDEXED>(a);
-    unsigned at = 0;
-    const GridLds grids = stage_grids(r, at, kRglLdsBlock);
-    if constexpr (MARG_ONLY) {
-        const SearchLdsMarg tv = stage_marg(r.vndf(), at, kRglLdsBlock);
-        const SearchLdsMarg tl = stage_marg(r.luminance(), at, kRglLdsBlock);
-        __syncthreads();
-        for (size_t j = (size_t)blockIdx.x * kRglLdsBlock + threadIdx.x; j < n_items; j += stride) rgl_unit<MODE, MASK>(a, r, grids, tv, tl, INDEXED ? (size_t)a.idx[j] : j);
-    } else {
-        const SearchLds tv = stage_search(r.vndf(), at, kRglLdsBlock);
-        const SearchLds tl = stage_search(r.luminance(), at, kRglLdsBlock);
-        __syncthreads();
-        for (size_t j = (size_t)blockIdx.x * kRglLdsBlock + threadIdx.x; j < n_items; j += stride) rgl_unit<MODE, MASK>(a, r, grids, tv, tl, INDEXED ? (size_t)a.idx[j] : j);
-    }
+    rgl_walk<rgl_lds_block(MODE, MASK), INDEXED, MARG_ONLY ? RGL_TABLES_LDS_MARG : RGL_TABLES_LDS>(
+        a, r, [&](const auto &g, const auto &tv, const auto &tl, size_t i) { rgl_unit<MODE, MASK>(a, r, g, tv, tl, i); });
 }
 
 // ---- spectral files: W values per unit at the wavelengths wl[i * W .. ) (nullptr: the file's own nodes) ----
@@ -364,25 +377,13 @@ __device__ __forceinline__ void rgl_unit_spectral(const BatchArgs &a, const RglD
 template <int MODE, bool LDS, int MASK = 0>
 __global__ __launch_bounds__(LDS ? rgl_lds_block(MODE) : kRglBlock) void k_rgl_spectral(BatchArgs a, RglDev r, const float *wl, int W)
 {
-    constexpr int kBlockThreads = LDS ? rgl_lds_block(MODE) : kRglBlock;
-    const size_t stride = (size_t)gridDim.x * kBlockThreads;
-    unsigned at = 0;
-    const GridLds grids = stage_grids(r, at, kBlockThreads);
-    if constexpr (LDS) {
-        const SearchLds tv = stage_search(r.vndf(), at, kBlockThreads);
-        const SearchLds tl = stage_search(r.luminance(), at, kBlockThreads);
-        __syncthreads();
-        for (size_t i = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; i < a.n; i += stride) rgl_unit_spectral<MODE, MASK>(a, r, grids, tv, tl, i, wl, W);
-    } else {
-        __syncthreads();
-        for (size_t i = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; i < a.n; i += stride)
-            rgl_unit_spectral<MODE, MASK>(a, r, grids, rgl::SearchMem(r.vndf()), rgl::SearchMem(r.luminance()), i, wl, W);
-    }
+    rgl_walk<LDS ? rgl_lds_block(MODE) : kRglBlock, false, LDS ? RGL_TABLES_LDS : RGL_TABLES_MEM>(
+        a, r, [&](const auto &g, const auto &tv, const auto &tl, size_t i) { rgl_unit_spectral<MODE, MASK>(a, r, g, tv, tl, i, wl, W); });
 }
 
 // ---- spectral files over a wavefront queue, or with a material id per unit ----
 // INDEXED: the units a.idx[0 .. min(*a.idx_count, a.n)); every read and write is at the queued slot (wl[i * W ..], out_rgb[i * W ..], ...)
-// and slots not in the queue are not touched.  !MULTI: the launch's one material, the body of k_rgl_spectral (grids in LDS, LDS: the
+// and slots not in the queue are not touched.  !MULTI: the launch's one material, the walk of k_rgl_spectral (grids in LDS, LDS: the
 // search tables as well).  MULTI: the material per unit from a.mat; a lane whose id names no live spectral RGL material writes zeros to
 // every output of its mode (W values, pdf, wo', pdf', W weights).
 template <int MODE>
@@ -402,32 +403,13 @@ __global__ __launch_bounds__(LDS ? rgl_lds_block(MODE) : kRglBlock) void k_rgl_s
 {
     static_assert(!(MULTI && LDS), "a batch with ids reads its materials' tables from memory");
     constexpr int kBlockThreads = LDS ? rgl_lds_block(MODE) : kRglBlock;
-    const size_t stride = (size_t)gridDim.x * kBlockThreads;
-    const size_t n_items = item_count<INDEXED>(a);
-    if constexpr (MULTI) {
-        for (size_t j = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; j < n_items; j += stride) {
-            const size_t i = INDEXED ? (size_t)a.idx[j] : j;
-            const int id = a.mat[i];
-            if (id < 0 || id >= a.n_materials || a.materials[id].kind != KIND_RGL_SPECTRAL) { spectral_zeros<MODE>(a, i, W); continue; }
-            // the descriptor into registers, whole (as k_rgl MULTI)
-            const RglDev rm = *(const RglDev *)a.materials[id].rgl;
-            rgl_unit_spectral<MODE, 0>(a, rm, rgl::GridMem{ rm.phi, rm.theta, rm.wavelengths }, rgl::SearchMem(rm.vndf()), rgl::SearchMem(rm.luminance()), i, wl, W);
-        }
-    } else {
-        unsigned at = 0;
-        const GridLds grids = stage_grids(r, at, kBlockThreads);
-        if constexpr (LDS) {
-            const SearchLds tv = stage_search(r.vndf(), at, kBlockThreads);
-            const SearchLds tl = stage_search(r.luminance(), at, kBlockThreads);
-            __syncthreads();
-            for (size_t j = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; j < n_items; j += stride)
-                rgl_unit_spectral<MODE, MASK>(a, r, grids, tv, tl, INDEXED ? (size_t)a.idx[j] : j, wl, W);
-        } else {
-            __syncthreads();
-            for (size_t j = (size_t)blockIdx.x * kBlockThreads + threadIdx.x; j < n_items; j += stride)
-                rgl_unit_spectral<MODE, MASK>(a, r, grids, rgl::SearchMem(r.vndf()), rgl::SearchMem(r.luminance()), INDEXED ? (size_t)a.idx[j] : j, wl, W);
-        }
-    }
+    if constexpr (MULTI)
+        rgl_walk_ids<kBlockThreads, INDEXED, KIND_RGL_SPECTRAL>(
+            a, [&](const RglDev &rm, const auto &g, const auto &tv, const auto &tl, size_t i) { rgl_unit_spectral<MODE, 0>(a, rm, g, tv, tl, i, wl, W); },
+            [&](size_t i) { spectral_zeros<MODE>(a, i, W); });
+    else
+        rgl_walk<kBlockThreads, INDEXED, LDS ? RGL_TABLES_LDS : RGL_TABLES_MEM>(
+            a, r, [&](const auto &g, const auto &tv, const auto &tl, size_t i) { rgl_unit_spectral<MODE, MASK>(a, r, g, tv, tl, i, wl, W); });
 }
 
 int lds_limit()
@@ -440,61 +422,70 @@ int lds_limit()
     return limit;
 }
 
-// a launch whose kernel keeps tables in dynamic LDS: raises the kernel's limit to `lds` bytes first
+// ---- one choice of route_rgl -> its instantiation, launched ----
+// grid: grid_blocks(a.n, block, compute units x blocks_per_cu); a kernel that keeps tables in LDS has its limit raised to lds_bytes first
 template <class... P>
-hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, P... args)
+hipError_t launch_kernel(void (*kernel)(P...), const RglChoice &k, size_t n, int compute_units, hipStream_t stream, P... args)
 {
-    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    if (k.tables != RGL_TABLES_MEM) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_bytes);
+    const dim3 grid(grid_blocks(n, (size_t)k.block, (size_t)compute_units * (size_t)k.blocks_per_cu)), block(k.block);
+    hipLaunchKernelGGL(kernel, grid, block, k.lds_bytes, stream, args...);
     return hipGetLastError();
 }
 
+// Names every instantiation a route can reach and no other: the kernels compiled for a bracket shape are the memory kernels (RGB: 5
+// and 15, spectral: 5), the full LDS form for isotropic files — anisotropic ones rarely fit — and the marginal-rows form of sample()
+// for anisotropic ones; material ids and every other combination take the kernel that tests the shape at run time.
 template <int MODE, int MASK>
-hipError_t launch_masked(const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream)
+hipError_t launch_choice(const RglChoice &k, const BatchArgs &a, const RglDev &r, const float *wl, int W, int compute_units, hipStream_t stream)
 {
-    // (kernels compiled for a bracket shape: the full LDS form for isotropic files — anisotropic ones rarely fit —, the marginal-rows
-    // form for anisotropic ones; the other combinations take the kernel that tests the shape at run time)
-    constexpr int kLdsMask = MASK == 5 ? 5 : 0, kMargMask = MASK == 15 ? 15 : 0;
-    // LDS variant: a single-material launch large enough to pay for the copy (one image of the running integrals per CU)
-    if (search == 0 && a.n >= (size_t)1 << 15) {
-        // one workgroup per CU
-        auto grid_of = [&](int threads) { return dim3(grid_blocks(a.n, (size_t)threads, (size_t)compute_units)); };
-        const size_t need = lds_bytes_of(*r), need_marg = lds_marg_bytes_of(*r);
-        if (need <= (size_t)lds_limit()) {
-            constexpr int kThreads = rgl_lds_block(MODE, kLdsMask);
-            return with_flags([&](auto ix) { return launch_with_lds(k_rgl_lds<MODE, ix, false, kLdsMask>, grid_of(kThreads), dim3(kThreads), need, stream, a, *r); },
-                              indexed);
-        }
-        // the marginal rows alone — sample() alone: eval / pdf read one marginal value per unit (not worth a copy per CU), and the fused
-        // unit of such a file is issued as two launches (launch_rgl)
-        if constexpr (MODE == MODE_SAMPLE) {
-            if (need_marg <= (size_t)lds_limit()) {
-                constexpr int kThreads = rgl_lds_block(MODE, kMargMask);
-                return with_flags([&](auto ix) {
-                    return launch_with_lds(k_rgl_lds<MODE, ix, true, kMargMask>, grid_of(kThreads), dim3(kThreads), need_marg, stream, a, *r);
-                }, indexed);
-            }
-        }
+    auto rgb = [&](auto kernel) { return launch_kernel(kernel, k, a.n, compute_units, stream, a, r); };
+    auto spectral = [&](auto kernel) { return launch_kernel(kernel, k, a.n, compute_units, stream, a, r, wl, W); };
+    const bool lds = k.tables == RGL_TABLES_LDS;
+    switch (k.family) {
+    case KERNEL_RGL:
+        if constexpr (MASK == 0)
+            if (k.multi) return with_flags([&](auto ix) { return rgb(k_rgl<MODE, ix, true>); }, k.indexed);
+        return with_flags([&](auto ix) { return rgb(k_rgl<MODE, ix, false, MASK>); }, k.indexed);
+    case KERNEL_RGL_LDS:
+        if constexpr (MODE == MODE_SAMPLE && MASK != 5)
+            if (k.tables == RGL_TABLES_LDS_MARG) return with_flags([&](auto ix) { return rgb(k_rgl_lds<MODE, ix, true, MASK>); }, k.indexed);
+        if constexpr (MASK != 15)
+            if (lds) return with_flags([&](auto ix) { return rgb(k_rgl_lds<MODE, ix, false, MASK>); }, k.indexed);
+        break;
+    case KERNEL_RGL_SPECTRAL:
+        if constexpr (MODE != MODE_PDF && MASK != 15) return with_flags([&](auto in_lds) { return spectral(k_rgl_spectral<MODE, in_lds, MASK>); }, lds);
+        break;
+    case KERNEL_RGL_SPECTRAL_Q:
+        if constexpr (MODE != MODE_PDF && MASK == 0)
+            if (k.multi) return with_flags([&](auto ix) { return spectral(k_rgl_spectral_q<MODE, ix, true, false>); }, k.indexed);
+        if constexpr (MODE != MODE_PDF && MASK != 15)
+            if (k.indexed) return with_flags([&](auto in_lds) { return spectral(k_rgl_spectral_q<MODE, true, false, in_lds, MASK>); }, lds);
+        break;
     }
-    const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
-    const size_t grids = grid_bytes_of(*r);                     // (at most 32 KB: 4,096 nodes per grid)
-    with_flags([&](auto ix) { hipLaunchKernelGGL((k_rgl<MODE, ix, false, MASK>), grid, block, grids, stream, a, *r); }, indexed);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
-template <int MODE>
-hipError_t launch_mode(const BatchArgs &a, const RglDev *r, bool indexed, int search, int compute_units, hipStream_t stream)
+// the launches of one call, in order on the stream; a route without launches: the call names no mode, or the pdf of a spectral file
+hipError_t launch_route(const RglRoute &route, const BatchArgs &a, const RglDev *r, const float *wl, int W, int compute_units, hipStream_t stream)
 {
-    if (!r) {                                                   // a batch with material ids: descriptors come from the material array
-        const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
-        const RglDev none{};
-        with_flags([&](auto ix) { hipLaunchKernelGGL((k_rgl<MODE, ix, true>), grid, block, 0, stream, a, none); }, indexed);
-        return hipGetLastError();
+    if (route.count == 0) return hipErrorInvalidValue;
+    const RglDev dev = r ? *r : RglDev{};                       // (material ids: descriptors come from the material array)
+    for (int l = 0; l < route.count; ++l) {
+        const RglChoice &k = route.launch[l];
+        const hipError_t e = with_mode(k.mode, [&](auto m) {
+            switch (k.mask) {
+            case 5:  return launch_choice<decltype(m)::value, 5>(k, a, dev, wl, W, compute_units, stream);
+            case 15: return launch_choice<decltype(m)::value, 15>(k, a, dev, wl, W, compute_units, stream);
+            default: return launch_choice<decltype(m)::value, 0>(k, a, dev, wl, W, compute_units, stream);
+            }
+        });
+        if (e != hipSuccess) return e;
     }
-    if (r->n_phi == 1 && r->n_theta > 1) return launch_masked<MODE, 5>(a, r, indexed, search, compute_units, stream);
-    if (r->n_phi > 1 && r->n_theta > 1) return launch_masked<MODE, 15>(a, r, indexed, search, compute_units, stream);
-    return launch_masked<MODE, 0>(a, r, indexed, search, compute_units, stream);
+    return hipSuccess;
 }
+
+RglShape shape_of(const RglDev *r) { return r ? RglShape{ r->n_phi, r->n_theta, r->nx, r->ny, r->n_wl } : RglShape{}; }
 
 bool all_finite(const float *p, size_t n)
 {
@@ -684,90 +675,67 @@ RglDev rgl_descriptor(const RglFields &f, const RglLayout &l, const float *base)
     return r;
 }
 
-namespace {
-template <int MODE, int MASK>
-hipError_t launch_spectral_masked(const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
+RglRoute route_rgl(int mode, bool spectral, bool multi, bool indexed, int search, size_t n, const RglShape &s, size_t lds_limit)
 {
-    if (search == 0 && a.n >= (size_t)1 << 15) {
-        const size_t need = lds_bytes_of(r);
-        if (need <= (size_t)lds_limit()) {
-            constexpr int kThreads = rgl_lds_block(MODE);
-            return launch_with_lds(k_rgl_spectral<MODE, true, MASK>, dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream, a, r, wl, W);
+    RglRoute route = { 0, {} };
+    // (the pdf of a spectral file is wavelength-free: the RGB pdf calls serve these materials)
+    if (mode < MODE_EVAL || mode > MODE_EVAL_PDF || (spectral && mode == MODE_PDF)) return route;
+    const int family = !spectral ? KERNEL_RGL : indexed || multi ? KERNEL_RGL_SPECTRAL_Q : KERNEL_RGL_SPECTRAL;
+    if (multi) {                                                // descriptors and tables come from behind each unit's material
+        route.launch[route.count++] = { family, mode, indexed, true, RGL_TABLES_MEM, 0, kRglBlock, 8, 0 };
+        return route;
+    }
+    // the bracket shape a kernel is compiled for (the database's spectral files are isotropic: no spectral kernel for 15)
+    const int mask = s.n_theta > 1 && s.n_phi == 1 ? 5 : s.n_theta > 1 && s.n_phi > 1 && !spectral ? 15 : 0;
+    // the LDS kernels: a launch large enough to pay for one copy of the running integrals per CU, one workgroup per CU
+    const bool copy = search == 0 && n >= (size_t)1 << 15, fits = lds_bytes_of(s) <= lds_limit;
+    auto one = [&](int m) {
+        RglChoice k = { family, m, indexed && family != KERNEL_RGL_SPECTRAL, false, RGL_TABLES_MEM, mask, kRglBlock, 8, grid_bytes_of(s) };  // (at most 32 KB: 4,096 nodes per grid)
+        if (copy && fits) {
+            k.tables = RGL_TABLES_LDS; k.mask = mask == 5 ? 5 : 0; k.lds_bytes = lds_bytes_of(s);
+        } else if (copy && !spectral && m == MODE_SAMPLE && lds_marg_bytes_of(s) <= lds_limit) {
+            // the marginal rows alone — sample() alone: eval / pdf read one marginal value per unit (not worth a copy per CU)
+            k.tables = RGL_TABLES_LDS_MARG; k.mask = mask == 15 ? 15 : 0; k.lds_bytes = lds_marg_bytes_of(s);
         }
-    }
-    hipLaunchKernelGGL((k_rgl_spectral<MODE, false, MASK>), dim3(rgl_grid(a.n, compute_units)), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
-    return hipGetLastError();
-}
-// (the database's spectral files are isotropic: that shape has its own kernels, every other one tests the shape at run time)
-template <int MODE>
-hipError_t launch_spectral_mode(const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
-{
-    if (r.n_phi == 1 && r.n_theta > 1) return launch_spectral_masked<MODE, 5>(a, r, wl, W, search, compute_units, stream);
-    return launch_spectral_masked<MODE, 0>(a, r, wl, W, search, compute_units, stream);
-}
-
-// a queue over one material: the launch choice of launch_spectral_masked
-template <int MODE, int MASK>
-hipError_t launch_spectral_queue_masked(const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
-{
-    if (search == 0 && a.n >= (size_t)1 << 15) {
-        const size_t need = lds_bytes_of(r);
-        if (need <= (size_t)lds_limit()) {
-            constexpr int kThreads = rgl_lds_block(MODE);
-            return launch_with_lds(k_rgl_spectral_q<MODE, true, false, true, MASK>, dim3(grid_blocks(a.n, kThreads, (size_t)compute_units)), dim3(kThreads), need, stream,
-                                   a, r, wl, W);
+        if (k.tables != RGL_TABLES_MEM) {
+            if (!spectral) k.family = KERNEL_RGL_LDS;
+            k.block = rgl_lds_block(m, spectral ? 0 : k.mask); k.blocks_per_cu = 1;
         }
-    }
-    hipLaunchKernelGGL((k_rgl_spectral_q<MODE, true, false, false, MASK>), dim3(rgl_grid(a.n, compute_units)), dim3(kRglBlock), grid_bytes_of(r), stream, a, r, wl, W);
-    return hipGetLastError();
-}
-template <int MODE>
-hipError_t launch_spectral_queue_mode(const BatchArgs &a, const RglDev *r, bool indexed, const float *wl, int W, int search, int compute_units, hipStream_t stream)
-{
-    if (!r) {                                                   // material ids: descriptors come from the material array
-        const dim3 grid(rgl_grid(a.n, compute_units)), block(kRglBlock);
-        const RglDev none{};
-        with_flags([&](auto ix) { hipLaunchKernelGGL((k_rgl_spectral_q<MODE, ix, true, false>), grid, block, 0, stream, a, none, wl, W); }, indexed);
-        return hipGetLastError();
-    }
-    if (!indexed) return launch_spectral_mode<MODE>(a, *r, wl, W, search, compute_units, stream);
-    if (r->n_phi == 1 && r->n_theta > 1) return launch_spectral_queue_masked<MODE, 5>(a, *r, wl, W, search, compute_units, stream);
-    return launch_spectral_queue_masked<MODE, 0>(a, *r, wl, W, search, compute_units, stream);
-}
-
-} // namespace
-
-hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
-{
-    if (a.n == 0) return hipSuccess;
-    const bool indexed = a.idx != nullptr;
-    return with_mode(mode, [&](auto m) -> hipError_t {
-        constexpr int M = decltype(m)::value;
-        if constexpr (M == MODE_PDF) return hipErrorInvalidValue;       // (the pdf is wavelength-free: the RGB pdf calls serve these materials)
-        else return launch_spectral_queue_mode<M>(a, r, indexed, wl, W, search, compute_units, stream);
-    });
-}
-
-hipError_t launch_rgl_spectral(int mode, const BatchArgs &a, const RglDev &r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
-{
-    if (a.n == 0) return hipSuccess;
-    return with_mode(mode, [&](auto m) { return launch_spectral_mode<decltype(m)::value>(a, r, wl, W, search, compute_units, stream); });
-}
-
-hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, int search, int compute_units, hipStream_t stream)
-{
-    if (a.n == 0) return hipSuccess;
-    const bool indexed = a.idx != nullptr;
+        route.launch[route.count++] = k;
+    };
     // The fused unit of a file whose integrals do not fit a CU's LDS (an anisotropic file: its lookups blend four slices of a 45 MB
     // image, the launch waits on L1 fills): eval + pdf and sample() as TWO launches on the stream.  The fused kernel carries sample()'s
     // 220 VGPRs through its eval as well (2 waves per SIMD); apart, eval + pdf runs at 3 waves per SIMD and sample() with its marginal
     // rows in LDS — 16M units: 3.84 ms fused, 3.34 ms apart (profiles/r04_rgl_rates.json); the 12 B per unit of wi read twice do not
     // show.  Same functions, same bits (the separate entry points are bit-compared with the fused one).
-    if (mode == MODE_EVAL_SAMPLE && r && search == 0 && a.n >= (size_t)1 << 15 && lds_bytes_of(*r) > (size_t)lds_limit()) {
-        const hipError_t e = launch_mode<MODE_EVAL_PDF>(a, r, indexed, search, compute_units, stream);
-        return e != hipSuccess ? e : launch_mode<MODE_SAMPLE>(a, r, indexed, search, compute_units, stream);
+    if (!spectral && mode == MODE_EVAL_SAMPLE && copy && !fits) { one(MODE_EVAL_PDF); one(MODE_SAMPLE); }
+    else one(mode);
+    return route;
+}
+
+std::string kernel_name(const RglChoice &k)
+{
+    auto b = [](bool x) { return x ? "true" : "false"; };
+    char s[96];
+    switch (k.family) {
+    case KERNEL_RGL_LDS:        snprintf(s, sizeof s, "k_rgl_lds<%d, %s, %s, %d>", k.mode, b(k.indexed), b(k.tables == RGL_TABLES_LDS_MARG), k.mask); break;
+    case KERNEL_RGL_SPECTRAL:   snprintf(s, sizeof s, "k_rgl_spectral<%d, %s, %d>", k.mode, b(k.tables == RGL_TABLES_LDS), k.mask); break;
+    case KERNEL_RGL_SPECTRAL_Q: snprintf(s, sizeof s, "k_rgl_spectral_q<%d, %s, %s, %s, %d>", k.mode, b(k.indexed), b(k.multi), b(k.tables == RGL_TABLES_LDS), k.mask); break;
+    default:                    snprintf(s, sizeof s, "k_rgl<%d, %s, %s, %d>", k.mode, b(k.indexed), b(k.multi), k.mask);
     }
-    return with_mode(mode, [&](auto m) { return launch_mode<decltype(m)::value>(a, r, indexed, search, compute_units, stream); });
+    return s;
+}
+
+hipError_t launch_rgl(int mode, const BatchArgs &a, const RglDev *r, int search, int compute_units, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    return launch_route(route_rgl(mode, false, !r, a.idx != nullptr, search, a.n, shape_of(r), (size_t)lds_limit()), a, r, nullptr, 0, compute_units, stream);
+}
+
+hipError_t launch_rgl_spectral_q(int mode, const BatchArgs &a, const RglDev *r, const float *wl, int W, int search, int compute_units, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    return launch_route(route_rgl(mode, true, !r, a.idx != nullptr, search, a.n, shape_of(r), (size_t)lds_limit()), a, r, wl, W, compute_units, stream);
 }
 
 } // namespace mrl

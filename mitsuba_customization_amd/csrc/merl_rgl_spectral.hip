@@ -53,8 +53,7 @@ int run_spectral(mrl_ctx *ctx, const BatchCall &c, bool queued = false, const ui
     auto launch = [&](const BatchCall &d) -> int {
         mrl::BatchArgs a = batch_args(ctx, d);
         a.idx = queue; a.idx_count = queue_count;
-        if (!d.mat && !queued) MRL_HIP(ctx, mrl::launch_rgl_spectral(d.mode, a, single->rgl, d.wl, W, ctx->rgl_search, ctx->compute_units, ctx->stream));
-        else MRL_HIP(ctx, mrl::launch_rgl_spectral_q(d.mode, a, single ? &single->rgl : nullptr, d.wl, W, ctx->rgl_search, ctx->compute_units, ctx->stream));
+        MRL_HIP(ctx, mrl::launch_rgl_spectral_q(d.mode, a, single ? &single->rgl : nullptr, d.wl, W, ctx->rgl_search, ctx->compute_units, ctx->stream));
         return MRL_OK;
     };
     if (kind == 1) return launch(c);

@@ -64,7 +64,7 @@ ABI_SYMBOLS = (
     "mrl_group_material_upload_rgl_spectral",
     "mrl_eval_spectral_queue", "mrl_eval_pdf_spectral_queue", "mrl_sample_spectral_queue", "mrl_eval_sample_spectral_queue",
     "mrl_eval_spectral_batch_mat", "mrl_eval_pdf_spectral_batch_mat", "mrl_sample_spectral_batch_mat", "mrl_eval_sample_spectral_batch_mat",
-    "mrl_table_grad_batch", "mrl_batch_route",
+    "mrl_table_grad_batch", "mrl_batch_route", "mrl_rgl_route",
 )
 # every symbol include/merl_hip_fit.h declares, the fitting extension of the ABI (exported by the same library)
 FIT_ABI_SYMBOLS = ("mrl_ggx_grad_batch",)
@@ -350,6 +350,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_group_plan.argtypes = [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(PlanOp), C.c_size_t]; L.mrl_group_plan.restype = C.c_size_t
     L.mrl_group_link_test.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(LinkReport)]
     L.mrl_batch_route.argtypes = [C.c_int] * 10 + [C.c_size_t, C.POINTER(RouteLaunch), C.c_size_t]; L.mrl_batch_route.restype = C.c_size_t
+    L.mrl_rgl_route.argtypes = [C.c_int] * 5 + [C.c_size_t] + [C.c_int] * 5 + [C.c_size_t, C.POINTER(RouteLaunch), C.c_size_t]; L.mrl_rgl_route.restype = C.c_size_t
     if path is None:
         _lib = L
     return L
@@ -1026,6 +1027,16 @@ def batch_route(mode: int, variant: int, layout: int, lookup: int, negative: int
     out = (RouteLaunch * 8)()
     got = L.mrl_batch_route(mode, variant, layout, lookup, negative, any_standard, material, queued, has_ggx, has_table, n, out, 8)
     assert got <= 8
+    return [(out[i].kernel.decode(), out[i].block, out[i].blocks_per_cu, bool(out[i].whole_xcds)) for i in range(got)]
+
+
+def rgl_route(mode: int, spectral: int, ids: int, queued: int, search: int, n: int, n_phi: int, n_theta: int, nx: int, ny: int, n_wl: int,
+              lds_limit: int):
+    """mrl_rgl_route: the kernels one call on an RGL material launches, in order, as (name, block, blocks_per_cu, whole_xcds) (needs no GPU)."""
+    L = load_library()
+    out = (RouteLaunch * 2)()
+    got = L.mrl_rgl_route(mode, spectral, ids, queued, search, n, n_phi, n_theta, nx, ny, n_wl, lds_limit, out, 2)
+    assert got <= 2
     return [(out[i].kernel.decode(), out[i].block, out[i].blocks_per_cu, bool(out[i].whole_xcds)) for i in range(got)]
 
 

@@ -1,13 +1,8 @@
 """The RGL kernels at the database's shapes and on files the other RGL tests never build: non-square tables, uneven parameter grids,
 distributions with regions without mass, an isotropic file on either side of the LDS fit boundary, 2^24-unit batches.  Every case
 goes against oracle/rgl_oracle.c (4,096 strided units and the batch's last 257) and holds the bit-identity invariants between entry
-points and kernels.  Which kernels a case reaches follows launch_rgl / launch_masked (csrc/merl_rgl.hip):
-  * a single-material call of n >= 2^15 units with MRL_OPT_RGL_SEARCH = 0 takes k_rgl_lds<M, ., false, 5 or 0> when lds_bytes_of(file)
-    <= the device's LDS per workgroup; else sample() takes k_rgl_lds<2, ., true, 15 or 0> (marginal rows in LDS), eval / pdf / eval_pdf
-    take k_rgl<M, ., false, mask> and the fused call is issued as eval_pdf + sample;
-  * n < 2^15 or MRL_OPT_RGL_SEARCH = 1: k_rgl<M, ., false, mask>;   a batch with material ids: k_rgl<M, ., true, 0>;
-  * spectral files: k_rgl_spectral<M, true, 5> when they fit, k_rgl_spectral<M, false, 5> from memory.
-mask: 5 isotropic (n_phi == 1, n_theta > 1), 15 anisotropic (n_phi > 1, n_theta > 1), 0 otherwise."""
+points and kernels.  Which kernels a case reaches is route_rgl (csrc/merl_kernels.hpp, exported as mrl_rgl_route); its rules are
+restated and checked without a device in tests/test_rgl_route_cpu.py, on these shapes among others."""
 import ctypes as C
 
 import numpy as np

@@ -54,7 +54,7 @@ def lib():
 
 
 def test_header_parses_to_the_binding_list():
-    assert len(PROTOTYPES) == 126
+    assert len(PROTOTYPES) == 127
     assert len(set(host.ABI_SYMBOLS)) == len(host.ABI_SYMBOLS)
     assert set(host.ABI_SYMBOLS) == set(PROTOTYPES)
 

@@ -10,7 +10,8 @@ Covers: RGB tables in the three parameterisations under MRL_OPT_KERNEL 0..4, bot
 and the renormalising blend; GGX alone, over two conductors and mixed with tables; n-channel tables of 1, 2, 4, 8, 32 channels;
 material ids (own, second, foreign kind, released, out of range, -1; another width for the n-channel calls); queues shorter than
 their capacity; host arrays in chunks smaller than n; an RGL and a spectral RGL file of tests/golden as whole arrays, queues and
-ids; one call of each direction-gradient family; the table adjoint one unit per call (larger adjoint calls sum with atomic adds in
+ids, and a synthetic one of the database's anisotropic shape (too large for a CU's LDS) at the large n; one call of each
+direction-gradient family; the table adjoint one unit per call (larger adjoint calls sum with atomic adds in
 no fixed order and do not repeat their own bits).  n in SIZES, and per family one n = a round of the largest grid + 37."""
 import os
 import sys
@@ -74,12 +75,12 @@ def run(out_path):
         for m in modes:
             call(f"{tag}/{m}", fns[m])
 
-    def rgb_queue_modes(g, tag, wi, wo, u, **kw):
+    def rgb_queue_modes(g, tag, wi, wo, u, modes=MODES, **kw):
         q, c = queue_of(wi.shape[0])
         fns = {"eval": lambda: g.eval_queue(wi, wo, q, c, **kw), "pdf": lambda: g.pdf_queue(wi, wo, q, c, **kw),
                "sample": lambda: g.sample_queue(wi, u, q, c, **kw), "eval_sample": lambda: g.eval_sample_queue(wi, wo, u, q, c, **kw),
                "eval_pdf": lambda: g.eval_pdf_queue(wi, wo, q, c, **kw)}
-        for m in MODES:
+        for m in modes:
             call(f"{tag}/queue/{m}", fns[m])
 
     def nch_modes(g, tag, c, wi, wo, u, queued=False, **kw):
@@ -199,7 +200,10 @@ def run(out_path):
         g.set_option(host.OPT_HOST_CHUNK, 100)
         nch_modes(g, f"nch4/s{sampling}/host_chunks", 4, hwi, hwo, hu, material=m[4][0])
         g.close()
-    # ---- RGL files of tests/golden: whole arrays, queues, ids
+    # ---- RGL files of tests/golden: whole arrays, queues, ids; and one file of the database's anisotropic shape, whose running integrals
+    # do not fit a CU's LDS as the small golden files' do: at `big` its sample() takes the marginal rows from LDS and its fused unit goes
+    # out as two launches
+    aniso_db = synth.make_rgl_fields(seed=10, n_phi=16, n_theta=8, res=32, res_ndf=128, res_sigma=32)
     for search in (0, 1):
         g = context()
         g.set_option(host.OPT_RGL_SEARCH, search)
@@ -230,6 +234,9 @@ def run(out_path):
                     call(f"spectral/r{search}/n{n}/queue/{kw_name}/eval", lambda: g.eval_spectral_queue(wi, wo, wl, q, c, **kw))
                     call(f"spectral/r{search}/n{n}/queue/{kw_name}/eval_pdf", lambda: g.eval_pdf_spectral_queue(wi, wo, wl, q, c, **kw))
                     call(f"spectral/r{search}/n{n}/queue/{kw_name}/sample", lambda: g.sample_spectral_queue(wi, u, wl, q, c, **kw))
+        db = g.upload_rgl(aniso_db)                                          # (wi, wo, u: the last n, big)
+        rgb_modes(g, f"rgl/r{search}/aniso_db/big", wi, wo, u, ("sample", "eval_pdf", "eval_sample"), material=db)
+        rgb_queue_modes(g, f"rgl/r{search}/aniso_db/big", wi, wo, u, ("sample", "eval_pdf", "eval_sample"), material=db)
         g.close()
     # ---- the direction gradients (their launchers' flag dispatch)
     for layout in (0, 1):
