@@ -7,7 +7,8 @@
 //   merl_host_stage.hpp    host-array path, host C++ only: stream list, slot layout, the chunk loop, the copy threads
 //   merl_image_cache.hip   on-disk cache of a material's device image
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
-//   merl_table_grad.hip    the adjoint of eval on an RGB table (mrl_table_grad_batch): scatter kernels + call
+//   merl_table_grad.hip    the adjoint of eval on RGB tables (mrl_table_grad_batch; with material ids and queues, onto several
+//                          tables: mrl_table_grad_batch_mat / mrl_table_grad_queue of merl_hip_fit_table.h): scatter kernels + calls
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
 //   merl_dir_grad.hpp      what the direction-gradient kernels share: the grid-stride loop with its masked stores, the record a
 //                          material id names, the PER_LANE / INDEXED dispatch; their one host call is grad_dir_call of merl_calls.hip
@@ -115,7 +116,7 @@ struct mrl_ctx {
     //   BUF_STAGE        one slot of a staged host-array call (slot_layout)
     //   BUF_QUEUES       kind-partitioned mixed batches: [2][n] unit indices + partition work area behind them
     //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
-    //   BUF_GRAD_BRICKS  mrl_table_grad_batch: gradient bricks, one 256-B record per table cell (merl_table_grad.hip)
+    //   BUF_GRAD_BRICKS  the table-gradient calls: gradient bricks, one 256-B record per cell of every table of a call (merl_table_grad.hip)
     //   BUF_GGX_GRAD     mrl_ggx_grad_batch: one 256-B row of partial sums per block + the sums of a host-array call (merl_ggx_grad.hip)
     enum { BUF_STAGE, BUF_QUEUES, BUF_PART_WORK, BUF_GRAD_BRICKS, BUF_GGX_GRAD, BUF_COUNT };
     DeviceBuf buf[BUF_COUNT];

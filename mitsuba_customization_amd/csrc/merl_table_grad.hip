@@ -1,6 +1,7 @@
-// merl_table_grad.hip — G += A^T g, the adjoint of eval on one RGB table material (include/merl_hip.h, mrl_table_grad_batch;
-// DESIGN.md §5g).  The forward kernels gather; this one scatters, and its destinations collide where measured BRDFs are
-// interesting.  The texels are never read: the call needs the material's dims, parameterisation and scale only, so one kernel
+// merl_table_grad.hip — G += A^T g, the adjoint of eval on RGB table materials: on one (include/merl_hip.h, mrl_table_grad_batch;
+// DESIGN.md §5g) and, with a material id per unit or over a wavefront queue, onto several target tables in one launch
+// (include/merl_hip_fit_table.h, mrl_table_grad_batch_mat / mrl_table_grad_queue).  The forward kernels gather;
+// this one scatters, and its destinations collide where measured BRDFs are interesting.  The texels are never read: the call needs the material's dims, parameterisation and scale only, so one kernel
 // serves both table layouts.
 //   k_grad_bricks   one lane = one unit: the f64 coordinate transform of eval, the Float corner weights; the wave then transposes
 //                   through LDS so that one wave-instruction carries the 24 values of two units (two contiguous 192-B segments of
@@ -8,7 +9,13 @@
 //   k_grad_fold     per texel: the sum of the brick slots that map to it (clamp / wrap folding), added into the caller's planar array
 //   k_grad_naive    the A/B baseline: each lane adds its 24 values straight into the planar array (64 lanes, 64 rows)
 // Gradient brick of cell (h0, d0, p0): 32 doubles, slot 3 k + ch for corner k = 4 a + 2 b + c (corner_weights' order), 24 used.
+// Each kernel body is written once, as a device function templated on PER_LANE (the unit's table is the target its material id
+// names: dims, parameterisation, scale and the first cell of the target's bricks come from a by-value descriptor array) and INDEXED
+// (the launch walks a queue).  k_grad_bricks / k_grad_naive are the <false, false> bodies, the single-material call's code;
+// k_grad_bricks_mat / k_grad_naive_mat<LOOKUP, INDEXED> the PER_LANE ones.  With targets the kernels work on a GLOBAL cell index,
+// cell_base + cell: two lanes are summed together only when they share target and cell.
 #include "merl_ctx.hpp"
+#include "../../include/merl_hip_fit_table.h"
 #include "merl_table_fast.hpp"
 
 namespace mrl {
@@ -19,16 +26,64 @@ constexpr int kBlock = 256;
 constexpr int kBrickSlots = 32;          // doubles per gradient brick (256 B)
 constexpr int kMergeMin = 4;             // merge a wave's lanes by cell when at least this many share the first live lane's cell
 
+// One target table of a launch with material ids: what the kernels need of it, by value in the kernel arguments (a queue call is
+// capturable in a HIP graph: nothing is copied from host memory at call time).  48 B
+struct GradTarget {
+    int id;                              // the material id a unit must carry
+    int n_th, n_td, n_pd, param;
+    int cell_base;                       // cells of the targets before it: its first brick, and a third of its planar offset
+    double scale[3];
+};
+// MRL_TABLE_GRAD_MAX_TARGETS descriptors are 768 B: GradArgs stays below 1 KiB of the 4 KiB a kernel's arguments may take
+constexpr int kMaxTargets = MRL_TABLE_GRAD_MAX_TARGETS;
+
 struct GradArgs {
     const float *wi, *wo, *g;
-    size_t n;
-    int n_th, n_td, n_pd, param;
+    size_t n;                            // units; of a queue launch the queue's capacity
+    int n_th, n_td, n_pd, param;         // the single-material launch's table
     Options opts;
     double scale[3];
-    double *bricks;                      // [cells][kBrickSlots]
-    double *planar;                      // k_grad_naive: [3][n_th][n_td][n_pd]
+    double *bricks;                      // [cells][kBrickSlots]; with targets: of all targets, end to end
+    double *planar;                      // k_grad_naive: [3][n_th][n_td][n_pd]; with targets: the targets' planar arrays end to end
     int merge;                           // 0: wave-uniform choice, 1: never, 2: always
+    // launches with targets (PER_LANE): a unit's material is mat[i], or single_id where mat is null
+    const int32_t *mat;
+    int32_t single_id;
+    const uint32_t *idx, *idx_count;     // INDEXED: the units idx[0 .. min(*idx_count, n))
+    int n_targets;
+    GradTarget targets[kMaxTargets];
 };
+
+// The table a unit adds into; known: false for a unit whose id names no target — it computes on target 0's shape and is masked
+struct GradShape {
+    int n_th, n_td, n_pd, param, cell_base;
+    double scale[3];
+    bool known;
+};
+__device__ __forceinline__ GradShape single_shape(const GradArgs &a)
+{
+    return { a.n_th, a.n_td, a.n_pd, a.param, 0, { a.scale[0], a.scale[1], a.scale[2] }, true };
+}
+// the target with this id: every lane walks all n_targets descriptors (a wave-uniform trip count, scalar loads) and selects
+__device__ __forceinline__ GradShape target_shape(const GradArgs &a, int id)
+{
+    const GradTarget &t0 = a.targets[0];
+    GradShape s = { t0.n_th, t0.n_td, t0.n_pd, t0.param, t0.cell_base, { t0.scale[0], t0.scale[1], t0.scale[2] }, false };
+    for (int k = 0; k < a.n_targets; ++k) {
+        const GradTarget &t = a.targets[k];
+        const bool hit = t.id == id;
+        s.n_th = hit ? t.n_th : s.n_th; s.n_td = hit ? t.n_td : s.n_td; s.n_pd = hit ? t.n_pd : s.n_pd;
+        s.param = hit ? t.param : s.param; s.cell_base = hit ? t.cell_base : s.cell_base;
+        s.scale[0] = hit ? t.scale[0] : s.scale[0]; s.scale[1] = hit ? t.scale[1] : s.scale[1]; s.scale[2] = hit ? t.scale[2] : s.scale[2];
+        s.known = s.known || hit;
+    }
+    return s;
+}
+template <bool INDEXED> __device__ __forceinline__ size_t grad_items(const GradArgs &a)
+{
+    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }      // every thread reads the same count
+    else return a.n;
+}
 
 // f64 add without a compare-and-swap loop (global_atomic_add_f64 / flat_atomic_add_f64); the destinations are device allocations
 __device__ __forceinline__ void add_f64(double *p, double v) { (void)unsafeAtomicAdd(p, v); }
@@ -42,12 +97,12 @@ struct GradUnit {
     double s[3];
 };
 
+// t: the unit's table (single_shape, or the target its id names), maps: that table's coordinate maps; in_range: unit i exists
 template <int LOOKUP>
-__device__ __forceinline__ GradUnit grad_unit(const GradArgs &a, const fast::TableMaps &maps, size_t i)
+__device__ __forceinline__ GradUnit grad_unit(const GradArgs &a, const GradShape &t, const fast::TableMaps &maps, size_t i, bool in_range)
 {
 #pragma clang fp contract(off)
     float wix = 0.0f, wiy = 0.0f, wiz = 0.0f, wox = 0.0f, woy = 0.0f, woz = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
-    const bool in_range = i < a.n;
     if (in_range) {
         load3(a.wi, i, wix, wiy, wiz);
         load3(a.wo, i, wox, woy, woz);
@@ -56,27 +111,39 @@ __device__ __forceinline__ GradUnit grad_unit(const GradArgs &a, const fast::Tab
     // the factor eval_tail multiplies by: Float wo.z (or 1), NaN when a component of either direction is not finite
     const float c32 = fast::cos_or_nan32((wix + wiy + wiz), wox, woy, woz, a.opts.cosine != 0);
     GradUnit u;
-    u.live = in_range && (wiz > 0.0f) && (woz > 0.0f) && (c32 == c32);
+    u.live = in_range && t.known && (wiz > 0.0f) && (woz > 0.0f) && (c32 == c32);
     const fast::Vec3 in = fast::normalize_f32(wix, wiy, wiz);
     const Coords c = maps(in, fast::dir_f32(wox, woy, woz));
     // eval's own cell and weights (a nearest lookup: all weight on corner 0)
-    u.cell = LOOKUP ? trilinear_cell(c, a.n_th, a.n_td, a.n_pd, a.opts.node, a.param) : nearest_cell(c, a.n_th, a.n_td, a.n_pd);
+    u.cell = LOOKUP ? trilinear_cell(c, t.n_th, t.n_td, t.n_pd, a.opts.node, t.param) : nearest_cell(c, t.n_th, t.n_td, t.n_pd);
     const CornerWeights cw = corner_weights(u.cell.fh, u.cell.fd, u.cell.fp);
 #pragma unroll
     for (int k = 0; k < 8; ++k) u.w[k] = u.live ? cw.w[k] : 0.0f;
     // a dead unit's coordinates are garbage: whatever they are, the cell stays inside the table (nearest_cell's already does)
     if constexpr (LOOKUP) {
-        u.cell.h0 = clampi(u.cell.h0, 0, a.n_th - 1); u.cell.d0 = clampi(u.cell.d0, 0, a.n_td - 1); u.cell.p0 = clampi(u.cell.p0, 0, a.n_pd - 1);
+        u.cell.h0 = clampi(u.cell.h0, 0, t.n_th - 1); u.cell.d0 = clampi(u.cell.d0, 0, t.n_td - 1); u.cell.p0 = clampi(u.cell.p0, 0, t.n_pd - 1);
     }
     const double cd = (double)c32;
-    u.s[0] = u.live ? a.scale[0] * cd * (double)g0 : 0.0;
-    u.s[1] = u.live ? a.scale[1] * cd * (double)g1 : 0.0;
-    u.s[2] = u.live ? a.scale[2] * cd * (double)g2 : 0.0;
+    u.s[0] = u.live ? t.scale[0] * cd * (double)g0 : 0.0;
+    u.s[1] = u.live ? t.scale[1] * cd * (double)g1 : 0.0;
+    u.s[2] = u.live ? t.scale[2] * cd * (double)g2 : 0.0;
     return u;
 }
 
-template <int LOOKUP>
-__global__ __launch_bounds__(kBlock) void k_grad_bricks(GradArgs a)
+// the table of the unit at queue position / index j (PER_LANE: its target's; a position past the end names no target)
+template <bool PER_LANE>
+__device__ __forceinline__ void unit_table(const GradArgs &a, size_t i, bool in_range, GradShape &shape, fast::TableMaps &maps)
+{
+    if constexpr (PER_LANE) {
+        int id = a.single_id;
+        if (a.mat) id = in_range ? a.mat[i] : -1;
+        shape = target_shape(a, id);
+        maps = fast::TableMaps(shape.n_th, shape.n_td, shape.n_pd, shape.param);
+    }
+}
+
+template <int LOOKUP, bool PER_LANE, bool INDEXED>
+__device__ __forceinline__ void grad_bricks(const GradArgs &a)
 {
     // what the lanes of a wave hand to each other: k-major, so that 64 lanes write 64 consecutive words.  The transposed reads take
     // one unit's values for all k (s_w[k][m]) and all channels (s_s[ch][m]) in one instruction: the rows are padded by one element so
@@ -84,18 +151,25 @@ __global__ __launch_bounds__(kBlock) void k_grad_bricks(GradArgs a)
     __shared__ int s_cell[kBlock];
     __shared__ float s_w[8][kBlock + 1];
     __shared__ double s_s[3][kBlock + 1];
-    const fast::TableMaps maps(a.n_th, a.n_td, a.n_pd, a.param);
+    GradShape shape = single_shape(a);                           // !PER_LANE: wave-uniform, formed once
+    fast::TableMaps maps(shape.n_th, shape.n_td, shape.n_pd, shape.param);
     const unsigned t = threadIdx.x, lane = t & 63u, wbase = t & ~63u;
     const unsigned sub = lane >> 5, slot = lane & 31u;           // two units per wave-instruction, 32 slots each (24 used)
     const unsigned k = slot / 3u, ch = slot - 3u * k;
     const bool slot_on = slot < (LOOKUP ? 24u : 3u);             // a nearest lookup has corner 0 only
     const unsigned kk = slot_on ? k : 0u, cc = slot_on ? ch : 0u;
     const size_t stride = (size_t)gridDim.x * kBlock;
-    const size_t rounds = (a.n + stride - 1) / stride;           // the same trip count for every thread: barriers inside
+    const size_t n_items = grad_items<INDEXED>(a);
+    const size_t rounds = (n_items + stride - 1) / stride;       // the same trip count for every thread: barriers inside
     for (size_t r = 0; r < rounds; ++r) {
-        const size_t i = r * stride + (size_t)blockIdx.x * kBlock + t;
-        const GradUnit u = grad_unit<LOOKUP>(a, maps, i);
-        const int cell = u.live ? cell_index<int>(u.cell, a.n_td, a.n_pd) : -1;
+        const size_t j = r * stride + (size_t)blockIdx.x * kBlock + t;
+        const bool in_range = j < n_items;
+        size_t i = j;
+        if constexpr (INDEXED) i = in_range ? (size_t)a.idx[j] : 0;
+        unit_table<PER_LANE>(a, i, in_range, shape, maps);
+        const GradUnit u = grad_unit<LOOKUP>(a, shape, maps, i, in_range);
+        // the global cell: of a launch without targets the table's own (cell_base is 0)
+        const int cell = u.live ? shape.cell_base + cell_index<int>(u.cell, shape.n_td, shape.n_pd) : -1;
         s_cell[t] = cell;
 #pragma unroll
         for (int q = 0; q < (LOOKUP ? 8 : 1); ++q) s_w[q][t] = u.w[q];
@@ -140,6 +214,11 @@ __global__ __launch_bounds__(kBlock) void k_grad_bricks(GradArgs a)
     }
 }
 
+template <int LOOKUP>
+__global__ __launch_bounds__(kBlock) void k_grad_bricks(GradArgs a) { grad_bricks<LOOKUP, false, false>(a); }
+template <int LOOKUP, bool INDEXED>
+__global__ __launch_bounds__(kBlock) void k_grad_bricks_mat(GradArgs a) { grad_bricks<LOOKUP, true, INDEXED>(a); }
+
 // the brick slots that reach texel i of an axis of n texels: source s = 0: cell i, corner offset 0; 1: cell i - 1, offset 1;
 // 2: the folded corner index n — cell n - 1, offset 1 — onto texel n - 1 (clamped axis) or texel 0 (periodic axis)
 __device__ __forceinline__ bool fold_source(int s, int i, int n, bool periodic, int &cell, int &off)
@@ -182,45 +261,63 @@ __global__ __launch_bounds__(kBlock) void k_grad_fold(const double *bricks, doub
     }
 }
 
-template <int LOOKUP>
-__global__ __launch_bounds__(kBlock) void k_grad_naive(GradArgs a)
+template <int LOOKUP, bool PER_LANE, bool INDEXED>
+__device__ __forceinline__ void grad_naive(const GradArgs &a)
 {
-    const fast::TableMaps maps(a.n_th, a.n_td, a.n_pd, a.param);
-    const size_t plane = (size_t)a.n_th * a.n_td * a.n_pd;
-    const bool periodic = param_phi_periodic(a.param);
+    GradShape shape = single_shape(a);
+    fast::TableMaps maps(shape.n_th, shape.n_td, shape.n_pd, shape.param);
     const size_t stride = (size_t)gridDim.x * kBlock;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
-        const GradUnit u = grad_unit<LOOKUP>(a, maps, i);
+    const size_t n_items = grad_items<INDEXED>(a);
+    for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < n_items; j += stride) {
+        const size_t i = INDEXED ? (size_t)a.idx[j] : j;
+        unit_table<PER_LANE>(a, i, true, shape, maps);
+        const GradUnit u = grad_unit<LOOKUP>(a, shape, maps, i, true);
         if (!u.live) continue;
+        const size_t plane = (size_t)shape.n_th * shape.n_td * shape.n_pd;
+        const bool periodic = param_phi_periodic(shape.param);
+        double *planar = a.planar + 3 * (size_t)shape.cell_base;       // the target's own planar array
 #pragma unroll
         for (int k = 0; k < (LOOKUP ? 8 : 1); ++k) {
             int h = u.cell.h0 + (k >> 2), d = u.cell.d0 + ((k >> 1) & 1), p = u.cell.p0 + (k & 1);
-            h = h == a.n_th ? a.n_th - 1 : h;
-            d = d == a.n_td ? a.n_td - 1 : d;
-            p = p == a.n_pd ? (periodic ? 0 : a.n_pd - 1) : p;
-            const size_t texel = ((size_t)h * a.n_td + d) * a.n_pd + p;
+            h = h == shape.n_th ? shape.n_th - 1 : h;
+            d = d == shape.n_td ? shape.n_td - 1 : d;
+            p = p == shape.n_pd ? (periodic ? 0 : shape.n_pd - 1) : p;
+            const size_t texel = ((size_t)h * shape.n_td + d) * shape.n_pd + p;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const double v = (double)u.w[k] * u.s[ch];
-                if (v != 0.0) add_f64(a.planar + ch * plane + texel, v);
+                if (v != 0.0) add_f64(planar + ch * plane + texel, v);
             }
         }
     }
 }
 
+template <int LOOKUP>
+__global__ __launch_bounds__(kBlock) void k_grad_naive(GradArgs a) { grad_naive<LOOKUP, false, false>(a); }
+template <int LOOKUP, bool INDEXED>
+__global__ __launch_bounds__(kBlock) void k_grad_naive_mat(GradArgs a) { grad_naive<LOOKUP, true, INDEXED>(a); }
+
 unsigned grad_grid(size_t n, int compute_units) { return grid_blocks(n, kBlock, (size_t)compute_units * 8); }
 
-// variant: MRL_OPT_TABLE_GRAD_KERNEL.  Bricks: adds the units' values into a.bricks (zeroed by the caller); naive: into a.planar
+// variant: MRL_OPT_TABLE_GRAD_KERNEL.  Bricks: adds the units' values into a.bricks (zeroed by the caller); naive: into a.planar.
+// a.n_targets > 0: the launch with targets (a.mat / a.single_id name a unit's table; a.idx: over a queue of capacity a.n)
 hipError_t launch_table_grad(GradArgs a, int variant, int compute_units, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
     const dim3 grid(grad_grid(a.n, compute_units)), block(kBlock);
-    if (variant == 1) {
-        with_flags([&](auto trilinear) { hipLaunchKernelGGL(k_grad_naive<trilinear ? 1 : 0>, grid, block, 0, stream, a); }, a.opts.lookup != 0);
+    const bool trilinear = a.opts.lookup != 0, indexed = a.idx != nullptr;
+    a.merge = variant == 2 ? 1 : (variant == 3 ? 2 : 0);
+    if (a.n_targets > 0) {
+        with_flags([&](auto tri, auto idx) {
+            if (variant == 1) hipLaunchKernelGGL((k_grad_naive_mat<tri ? 1 : 0, idx>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_grad_bricks_mat<tri ? 1 : 0, idx>), grid, block, 0, stream, a);
+        }, trilinear, indexed);
         return hipGetLastError();
     }
-    a.merge = variant == 2 ? 1 : (variant == 3 ? 2 : 0);
-    with_flags([&](auto trilinear) { hipLaunchKernelGGL(k_grad_bricks<trilinear ? 1 : 0>, grid, block, 0, stream, a); }, a.opts.lookup != 0);
+    with_flags([&](auto tri) {
+        if (variant == 1) hipLaunchKernelGGL(k_grad_naive<tri ? 1 : 0>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(k_grad_bricks<tri ? 1 : 0>, grid, block, 0, stream, a);
+    }, trilinear);
     return hipGetLastError();
 }
 
@@ -238,65 +335,63 @@ hipError_t launch_table_grad_fold(const double *bricks, double *planar, const in
 
 using namespace mrlabi;
 
-extern "C" {
+namespace {
 
-int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, int32_t id, size_t n, double *grad_planar)
+// One table of a call: its bricks start at cell_base records into the workspace, its planar array at 3 cell_base doubles
+struct GradTable { int dims[3]; int param; size_t cell_base; };
+
+// What every table-gradient call does once its arguments are checked.  streams: wi, wo, grad_rgb and (at_mat >= 0) mat; kind: 1 device
+// pointers, 0 host arrays; a: everything but the arrays (a.idx: a queue — device pointers only); tables: the call's tables, `cells`
+// cells in all.  The workspace is cleared once and folded once, table by table, into the tables' own slices and nothing else.
+int run_table_grad(mrl_ctx *ctx, mrl::GradArgs a, const StreamList &streams, int at_mat, size_t n, const std::vector<GradTable> &tables, size_t cells,
+                   double *grad_planar, int kind)
 {
-    if (!ctx) return MRL_ERR_INVALID;
-    MRL_GUARD(ctx);
-    if (n == 0) return MRL_OK;
-    const StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
-    if (first_null(streams) || !grad_planar) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    if (id < 0 || (size_t)id >= ctx->materials.size() || ctx->materials[(size_t)id].released) return fail(ctx, MRL_ERR_MATERIAL, "unknown material id");
-    const MaterialHost &mh = ctx->materials[(size_t)id];
-    if (mh.dev.kind != mrl::KIND_MERL && mh.dev.kind != mrl::KIND_TABLE)
-        return fail(ctx, MRL_ERR_MATERIAL, "the table gradient is defined for RGB table materials (MERL / customized_measurement)");
-    if (!mh.has_scale) return fail(ctx, MRL_ERR_MATERIAL, "a table restored from an image file does not carry its channel scales");
-    if (ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
-        return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise makes eval non-linear in the table: no adjoint");
-    MRL_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = common_kind({ grad_planar }, streams);
-    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
-
-    const int dims[3] = { mh.dev.n_th, mh.dev.n_td, mh.dev.n_pd };
-    const size_t plane = (size_t)dims[0] * dims[1] * dims[2];
     const int variant = ctx->table_grad_kernel;
-    mrl::GradArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_th = dims[0]; a.n_td = dims[1]; a.n_pd = dims[2]; a.param = mh.dev.param;
-    a.opts = ctx->opts;
-    a.scale[0] = mh.scale[0]; a.scale[1] = mh.scale[1]; a.scale[2] = mh.scale[2];
     if (variant != 1) {
         DeviceBuf &bricks = ctx->buf[mrl_ctx::BUF_GRAD_BRICKS];      // one 256-B record per table cell; grown on demand, reused
-        const int rc = bricks.reserve(ctx, plane * mrl::kBrickSlots * sizeof(double));
+        const int rc = bricks.reserve(ctx, cells * mrl::kBrickSlots * sizeof(double));
         if (rc != MRL_OK) return rc;
         a.bricks = (double *)bricks.p;
-        MRL_HIP(ctx, hipMemsetAsync(a.bricks, 0, plane * mrl::kBrickSlots * sizeof(double), ctx->stream));
+        MRL_HIP(ctx, hipMemsetAsync(a.bricks, 0, cells * mrl::kBrickSlots * sizeof(double), ctx->stream));
     }
-    if (kind == 1) {
-        a.wi = wi; a.wo = wo; a.g = grad_rgb; a.n = n; a.planar = grad_planar;
-        MRL_HIP(ctx, mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream));
-        if (variant != 1) MRL_HIP(ctx, mrl::launch_table_grad_fold(a.bricks, grad_planar, dims, a.param, ctx->compute_units, ctx->stream));
+    auto on = [&](char *const *addr, size_t m) {
+        a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
+        a.mat = at_mat >= 0 ? (const int32_t *)addr[at_mat] : nullptr;
+    };
+    auto fold = [&](double *planar) -> int {
+        if (variant == 1) return MRL_OK;
+        for (const GradTable &t : tables)
+            MRL_HIP(ctx, mrl::launch_table_grad_fold(a.bricks + t.cell_base * mrl::kBrickSlots, planar + 3 * t.cell_base, t.dims, t.param,
+                                                     ctx->compute_units, ctx->stream));
         return MRL_OK;
+    };
+    if (kind == 1) {
+        char *addr[4];
+        for (size_t k = 0; k < streams.size(); ++k) addr[k] = (char *)streams[k].ptr;
+        on(addr, n);
+        a.planar = grad_planar;
+        MRL_HIP(ctx, mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream));
+        return fold(grad_planar);
     }
     // host arrays: the inputs are staged chunk by chunk, the sums gathered in a device array and added to the caller's on the host
     double *d_planar = nullptr;
-    MRL_ALLOC(ctx, hipMalloc((void **)&d_planar, 3 * plane * sizeof(double)));
+    MRL_ALLOC(ctx, hipMalloc((void **)&d_planar, 3 * cells * sizeof(double)));
     auto run = [&]() -> int {
-        MRL_HIP(ctx, hipMemsetAsync(d_planar, 0, 3 * plane * sizeof(double), ctx->stream));
+        MRL_HIP(ctx, hipMemsetAsync(d_planar, 0, 3 * cells * sizeof(double), ctx->stream));
         a.planar = d_planar;
-        const int rc = run_host_staged(ctx, streams, n, 0, [&](char *const *addr, size_t m) -> int {
-            a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
+        int rc = run_host_staged(ctx, streams, n, 0, [&](char *const *addr, size_t m) -> int {
+            on(addr, m);
             MRL_HIP(ctx, mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream));
             return MRL_OK;
         });
         if (rc != MRL_OK) return rc;
-        if (variant != 1) MRL_HIP(ctx, mrl::launch_table_grad_fold(a.bricks, d_planar, dims, a.param, ctx->compute_units, ctx->stream));
+        rc = fold(d_planar);
+        if (rc != MRL_OK) return rc;
         std::vector<double> sums;
-        try { sums.resize(3 * plane); } catch (const std::bad_alloc &) { return fail(ctx, MRL_ERR_OOM, "gradient buffer"); }
-        MRL_HIP(ctx, hipMemcpyAsync(sums.data(), d_planar, 3 * plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        try { sums.resize(3 * cells); } catch (const std::bad_alloc &) { return fail(ctx, MRL_ERR_OOM, "gradient buffer"); }
+        MRL_HIP(ctx, hipMemcpyAsync(sums.data(), d_planar, 3 * cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         MRL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t t = 0; t < 3 * plane; ++t)
+        for (size_t t = 0; t < 3 * cells; ++t)
             if (sums[t] != 0.0) grad_planar[t] += sums[t];
         return MRL_OK;
     };
@@ -306,4 +401,126 @@ int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const f
     return rc;
 }
 
+// is `id` a table the adjoint is defined for?  MRL_OK, or the failure mrl_table_grad_batch documents
+int check_grad_table(mrl_ctx *ctx, int32_t id)
+{
+    if (id < 0 || (size_t)id >= ctx->materials.size() || ctx->materials[(size_t)id].released) return fail(ctx, MRL_ERR_MATERIAL, "unknown material id");
+    const MaterialHost &mh = ctx->materials[(size_t)id];
+    if (mh.dev.kind != mrl::KIND_MERL && mh.dev.kind != mrl::KIND_TABLE)
+        return fail(ctx, MRL_ERR_MATERIAL, "the table gradient is defined for RGB table materials (MERL / customized_measurement)");
+    if (!mh.has_scale) return fail(ctx, MRL_ERR_MATERIAL, "a table restored from an image file does not carry its channel scales");
+    return MRL_OK;
+}
+
+// mrl_table_grad_batch_mat / mrl_table_grad_queue (include/merl_hip_fit_table.h); queued: over queue[0 .. min(*queue_count, n)), n its capacity
+int table_grad_targets(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id, size_t n,
+                       bool queued, const uint32_t *queue, const uint32_t *queue_count, const int32_t *target_ids, int n_targets, double *grad_planar)
+{
+    if (!ctx) return MRL_ERR_INVALID;
+    MRL_GUARD(ctx);
+    if (n == 0) return MRL_OK;
+    StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
+    if (first_null(streams) || !grad_planar || !target_ids || (queued && (!queue || !queue_count))) return fail(ctx, MRL_ERR_INVALID, "null array argument");
+    int at_mat = -1;
+    if (mat) { at_mat = (int)streams.size(); streams.push_back({ (void *)mat, 4, false, "mat" }); }
+    if (n_targets < 1 || n_targets > MRL_TABLE_GRAD_MAX_TARGETS)
+        return fail(ctx, MRL_ERR_INVALID, "n_targets must be 1.." + std::to_string(MRL_TABLE_GRAD_MAX_TARGETS));
+    mrl::GradArgs a;
+    std::memset(&a, 0, sizeof a);
+    int dims[MRL_TABLE_GRAD_MAX_TARGETS][3];
+    for (int k = 0; k < n_targets; ++k) {
+        const int rc = check_grad_table(ctx, target_ids[k]);
+        if (rc != MRL_OK) return rc;
+        for (int j = 0; j < k; ++j)
+            if (target_ids[j] == target_ids[k]) return fail(ctx, MRL_ERR_INVALID, "a material is listed twice among the targets");
+        const MaterialHost &mh = ctx->materials[(size_t)target_ids[k]];
+        mrl::GradTarget &t = a.targets[k];
+        t.id = target_ids[k];
+        dims[k][0] = t.n_th = mh.dev.n_th; dims[k][1] = t.n_td = mh.dev.n_td; dims[k][2] = t.n_pd = mh.dev.n_pd; t.param = mh.dev.param;
+        t.scale[0] = mh.scale[0]; t.scale[1] = mh.scale[1]; t.scale[2] = mh.scale[2];
+    }
+    // where each target's bricks and planar array start: the one place that adds the cells up and bounds the int global cell index
+    size_t offsets[MRL_TABLE_GRAD_MAX_TARGETS + 1];
+    if (mrl_table_grad_layout(&dims[0][0], n_targets, offsets) != MRL_OK)
+        return fail(ctx, MRL_ERR_INVALID, "the targets have more than 2^31 - 1 cells in all");
+    std::vector<GradTable> tables;
+    for (int k = 0; k < n_targets; ++k) {
+        a.targets[k].cell_base = (int)(offsets[k] / 3);
+        tables.push_back({ { dims[k][0], dims[k][1], dims[k][2] }, a.targets[k].param, offsets[k] / 3 });
+    }
+    const size_t cells = offsets[n_targets] / 3;
+    a.n_targets = n_targets;
+    if (ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
+        return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise makes eval non-linear in the table: no adjoint");
+    if (queued && n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
+    MRL_HIP(ctx, hipSetDevice(ctx->device));
+    const int kind = queued ? common_kind({ grad_planar, queue, queue_count }, streams) : common_kind({ grad_planar }, streams);
+    if (queued && kind != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
+    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
+    a.opts = ctx->opts;
+    a.single_id = single_id;
+    a.idx = queue; a.idx_count = queue_count;
+    return run_table_grad(ctx, a, streams, at_mat, n, tables, cells, grad_planar, kind);
+}
+
+} // namespace
+
+extern "C" {
+
+int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, int32_t id, size_t n, double *grad_planar)
+{
+    if (!ctx) return MRL_ERR_INVALID;
+    MRL_GUARD(ctx);
+    if (n == 0) return MRL_OK;
+    const StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
+    if (first_null(streams) || !grad_planar) return fail(ctx, MRL_ERR_INVALID, "null array argument");
+    int rc = check_grad_table(ctx, id);
+    if (rc != MRL_OK) return rc;
+    const MaterialHost &mh = ctx->materials[(size_t)id];
+    if (ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
+        return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise makes eval non-linear in the table: no adjoint");
+    MRL_HIP(ctx, hipSetDevice(ctx->device));
+    const int kind = common_kind({ grad_planar }, streams);
+    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
+
+    mrl::GradArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_th = mh.dev.n_th; a.n_td = mh.dev.n_td; a.n_pd = mh.dev.n_pd; a.param = mh.dev.param;
+    a.opts = ctx->opts;
+    a.scale[0] = mh.scale[0]; a.scale[1] = mh.scale[1]; a.scale[2] = mh.scale[2];
+    const size_t plane = (size_t)a.n_th * a.n_td * a.n_pd;
+    return run_table_grad(ctx, a, streams, -1, n, { { { a.n_th, a.n_td, a.n_pd }, a.param, 0 } }, plane, grad_planar, kind);
+}
+
+int mrl_table_grad_layout(const int *dims, int n_targets, size_t *offsets_out)
+{
+    if (!dims || n_targets < 1 || n_targets > MRL_TABLE_GRAD_MAX_TARGETS) return MRL_ERR_INVALID;
+    uint64_t cells = 0;                                   // three ints multiply to at most 2^93: checked factor by factor
+    for (int k = 0; k < n_targets; ++k) {
+        const int *d = dims + 3 * k;
+        if (d[0] < 1 || d[1] < 1 || d[2] < 1) return MRL_ERR_INVALID;
+        const uint64_t rows = (uint64_t)d[0] * (uint64_t)d[1];
+        if (rows > (uint64_t)INT32_MAX) return MRL_ERR_INVALID;
+        if (offsets_out) offsets_out[k] = (size_t)(3 * cells);
+        cells += rows * (uint64_t)d[2];                   // at most 2^62 + 2^31
+        if (cells > (uint64_t)INT32_MAX) return MRL_ERR_INVALID;
+    }
+    if (offsets_out) offsets_out[n_targets] = (size_t)(3 * cells);
+    return MRL_OK;
+}
+
+int mrl_table_grad_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id, size_t n,
+                             const int32_t *target_ids, int n_targets, double *grad_planar)
+{
+    return table_grad_targets(ctx, wi, wo, grad_rgb, mat, single_id, n, false, nullptr, nullptr, target_ids, n_targets, grad_planar);
+}
+
+int mrl_table_grad_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id,
+                         const uint32_t *queue, const uint32_t *queue_count, size_t capacity, const int32_t *target_ids, int n_targets,
+                         double *grad_planar)
+{
+    return table_grad_targets(ctx, wi, wo, grad_rgb, mat, single_id, capacity, true, queue, queue_count, target_ids, n_targets, grad_planar);
+}
+
 } // extern "C"
+

@@ -1,6 +1,7 @@
 """From measurements (wi, wo, rgb) to a material.
 A table: the normalised splat and CGLS on |A T - y|^2, built on MerlHip.eval (A) and MerlHip.table_grad (A^T).  numpy arrays in ->
-numpy out, device tensors in -> device tensors out.
+numpy out, device tensors in -> device tensors out.  splat_mat / fit_tables do the same for several tables at once from one
+interleaved measurement set with a table index per unit, on MerlHip.table_grad_mat: one launch serves all tables.
 A GGX conductor (alpha, eta[3], k[3]): Levenberg-Marquardt on sum w (eval - y)^2, built on MerlHip.eval and MerlHip.ggx_grad
 (fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).
 
@@ -83,6 +84,110 @@ def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
     finally:
         ctx.release_material(shape_mid)
     return x, residuals
+
+
+# ---- several tables from one interleaved measurement set (MerlHip.table_grad_mat: one launch for all tables) ----
+def _per_table(value, count, default):
+    return [default] * count if value is None else list(value)
+
+
+def _unit_ids(mat, ids):
+    """The material id of every unit: ids[mat[i]], or -1 (no material) where mat[i] is not an index into ids.  int32, like mat."""
+    k = len(ids)
+    if host._is_tensor(mat):
+        import torch
+        table = torch.tensor(list(ids) + [-1], dtype=torch.int32, device=mat.device)
+        return table[torch.where((mat >= 0) & (mat < k), mat, torch.full_like(mat, k)).long()].contiguous()
+    table = np.array(list(ids) + [-1], np.int32)
+    return np.ascontiguousarray(table[np.where((mat >= 0) & (mat < k), mat, k)])
+
+
+def _upload_all(ctx, tables, params, scales):
+    ids = []
+    try:
+        for t, p, s in zip(tables, params, scales):
+            ids.append(_upload(ctx, t, p, s))
+    except Exception:
+        for mid in ids:
+            ctx.release_material(mid)
+        raise
+    return ids
+
+
+def splat_mat(ctx, dims_list, wi, wo, mat, rgb, params=None, scales=None):
+    """splat() for K tables at once: unit i belongs to table mat[i] (int32, an index into dims_list; any other value: to none).
+    Two launches of table_grad_mat serve all tables.  Returns (tables, masks), tuples of K arrays like splat()'s."""
+    k = len(dims_list)
+    params, scales = _per_table(params, k, None), _per_table(scales, k, (1.0, 1.0, 1.0))
+    ids = _upload_all(ctx, [np.ones((3,) + tuple(d)) for d in dims_list], params, scales)
+    try:
+        unit = _unit_ids(mat, ids)
+        num = ctx.table_grad_mat(wi, wo, _f32(rgb), ids, mat=unit)
+        den = ctx.table_grad_mat(wi, wo, ctx.eval(wi, wo, mat=unit), ids, mat=unit)
+    finally:
+        for mid in ids:
+            ctx.release_material(mid)
+    masks = tuple(d > 0 for d in den)
+    return tuple(n / (d + ~m) * m for n, d, m in zip(num, den, masks)), masks
+
+
+def fit_tables(ctx, dims_list, wi, wo, mat, rgb, iters, params=None, scales=None):
+    """fit_table() for K tables from one interleaved measurement set: K independent CGLS problems driven by shared launches — per
+    iteration one eval with material ids and one table_grad_mat, whatever K.  The step lengths, the conjugation factors and the
+    residuals are kept per table, from dot products over that table's units.  mat: as in splat_mat(); what a unit of no table
+    measured is never read into a sum (it may be NaN).
+    Returns (tables, residuals): K arrays f64 [3, *dims_k] and K lists [|A_k T_k - y_k| for iteration 0 .. iters]."""
+    if ctx.get_option(host.OPT_NEGATIVE) != 1:
+        raise ValueError("fit_tables needs OPT_NEGATIVE = 1 (keep): the iterates have negative entries and a clamped upload is not linear")
+    k = len(dims_list)
+    params, scales = _per_table(params, k, None), _per_table(scales, k, (1.0, 1.0, 1.0))
+    y = _f64(rgb)
+    x = list(splat_mat(ctx, dims_list, wi, wo, mat, rgb, params, scales)[0])
+    member = [mat == j for j in range(k)]                            # [n] masks: the units of table j
+    weight = [_f64(m)[:, None] for m in member]
+    shape_ids = _upload_all(ctx, [np.ones((3,) + tuple(d)) for d in dims_list], params, scales)
+    shape_unit = _unit_ids(mat, shape_ids)
+
+    def A(tables):
+        ids = _upload_all(ctx, tables, params, scales)
+        try:
+            return _f64(ctx.eval(wi, wo, mat=_unit_ids(mat, ids)))
+        finally:
+            for mid in ids:
+                ctx.release_material(mid)
+
+    def At(r):
+        return ctx.table_grad_mat(wi, wo, _f32(r), shape_ids, mat=shape_unit)
+
+    def unit_dots(a):                                               # per table: the dot product of a with itself over its units
+        rows = (a * a).sum(1)                                       # (selected, not weighted: a unit of no table may hold NaN)
+        return [float(rows[m].sum()) for m in member]
+
+    try:
+        r = y - A(x)
+        s = At(r)
+        p = list(s)
+        gamma = [_dot(sj, sj) for sj in s]
+        residuals = [[rr ** 0.5] for rr in unit_dots(r)]
+        for _ in range(iters):
+            qq = unit_dots(q := A(p))
+            alpha = [g / d if g != 0.0 and d != 0.0 else 0.0 for g, d in zip(gamma, qq)]
+            for j in range(k):
+                x[j] = x[j] + alpha[j] * p[j]
+            r = r - sum(a * w for a, w in zip(alpha, weight)) * q
+            s = At(r)
+            for j in range(k):
+                if alpha[j] == 0.0:                                 # a table that has converged (or has no unit) stays as it is
+                    continue
+                gamma_new = _dot(s[j], s[j])
+                p[j] = s[j] + (gamma_new / gamma[j]) * p[j]
+                gamma[j] = gamma_new
+            for j, rr in enumerate(unit_dots(r)):
+                residuals[j].append(rr ** 0.5 if alpha[j] != 0.0 else residuals[j][-1])
+    finally:
+        for mid in shape_ids:
+            ctx.release_material(mid)
+    return tuple(x), residuals
 
 
 # ---- GGX conductor: Levenberg-Marquardt in q = (ln alpha, ln eta[3], k[3]) ----

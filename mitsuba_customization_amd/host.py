@@ -74,6 +74,9 @@ DIFF_ABI_SYMBOLS = ("mrl_ggx_grad_dir_batch", "mrl_ggx_grad_dir_queue")
 DIFF_TABLE_ABI_SYMBOLS = ("mrl_table_grad_dir_batch", "mrl_table_grad_dir_queue")
 # every symbol include/merl_hip_diff_nch.h declares: the same gradient on n-channel table materials
 DIFF_NCH_ABI_SYMBOLS = ("mrl_table_grad_dir_batch_nch", "mrl_table_grad_dir_queue_nch")
+# every symbol include/merl_hip_fit_table.h declares: the table adjoint with a material id per unit and over wavefront queues
+FIT_TABLE_ABI_SYMBOLS = ("mrl_table_grad_batch_mat", "mrl_table_grad_queue", "mrl_table_grad_layout")
+TABLE_GRAD_MAX_TARGETS = 16         # MRL_TABLE_GRAD_MAX_TARGETS
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -215,11 +218,17 @@ _FAMILIES = {               # family: (symbol, the parameters between the inputs
     "group":              ("mrl_group_{}_batch", ("mat", "single_id", "n")),          # first argument: the group, not a context
 }
 _PDF_FAMILIES = ("batch", "queue", "group")         # the pdf is channel- and wavelength-free: the other families have no pdf mode
-_SCALARS = {"single_id": C.c_int32, "id": C.c_int32, "n": C.c_size_t, "capacity": C.c_size_t, "n_channels": C.c_int, "n_wavelengths": C.c_int}
+_SCALARS = {"single_id": C.c_int32, "id": C.c_int32, "n": C.c_size_t, "capacity": C.c_size_t, "n_channels": C.c_int, "n_wavelengths": C.c_int,
+            "n_targets": C.c_int}
 # (family, mode): (symbol, middle parameters, inputs, outputs)
 _CALLS = {(family, mode): (symbol.format(mode), middle) + streams
           for family, (symbol, middle) in _FAMILIES.items() for mode, streams in _MODES.items()
           if mode != "pdf" or family in _PDF_FAMILIES}
+# the table adjoint with targets (include/merl_hip_fit_table.h): the same rows — three input streams, the middle parameters, and no
+# [n, ...] output: what the calls add into, grad_planar, is one of the middle parameters (supplied by the caller of _stream_call)
+_TARGETS = ("target_ids", "n_targets", "grad_planar")
+_CALLS["batch", "table_grad_mat"] = ("mrl_table_grad_batch_mat", _FAMILIES["batch"][1] + _TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
+_CALLS["queue", "table_grad_mat"] = ("mrl_table_grad_queue", _FAMILIES["queue"][1] + _TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
 
 
 _lib = None
@@ -272,6 +281,7 @@ def load_library(path: Optional[str] = None):
         getattr(L, symbol).argtypes = [vp] + [fp] * len(ins) + [_SCALARS.get(name, vp) for name in middle] + [fp] * len(outs)
     L.mrl_partition_by_material.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
+    L.mrl_table_grad_layout.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_size_t)]
     L.mrl_ggx_grad_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int32, C.c_size_t, vp, vp]
     L.mrl_ggx_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
@@ -382,7 +392,8 @@ def _addr(x, dtype, cols: Optional[int], n: Optional[int], name: str):
     return ptr
 
 
-def _stream_call(owner, family, mode, ins, out=None, width=3, wavelengths=None, mat=None, material=0, queue=None, count=None, capacity=None):
+def _stream_call(owner, family, mode, ins, out=None, width=3, wavelengths=None, mat=None, material=0, queue=None, count=None, capacity=None,
+                 more=None):
     """One batch or queue call of a MerlHip (family "group": of a MerlGroup) from its row of _CALLS.  ins: the mode's input arrays in ABI
     order; n is wi's length.  Outputs the caller does not pass in `out` are allocated: like wi for whole arrays, zeros on wi's device for a
     queue (unqueued slots are never written), numpy for a group.  Returns the output, or the outputs as a tuple in ABI order."""
@@ -414,12 +425,27 @@ def _stream_call(owner, family, mode, ins, out=None, width=3, wavelengths=None, 
                "n_channels": width, "n_wavelengths": width, "wavelengths": _addr(wavelengths, np.float32, width, n, "wavelengths")}
     if queued:
         between.update(queue=q, queue_count=q_count, capacity=cap)
+    between.update(more or {})                          # middle parameters only some rows have
     args = [owner._g if family == "group" else owner._ctx]
     args += [_addr(x, np.float32, cols, n, name) for (name, cols), x in zip(in_streams, ins)]
     args += [between[name] for name in middle]
     args += [_addr(x, np.float32, width if cols == 0 else cols, n, name) for (name, cols), x in zip(out_streams, out)]
     owner._check(getattr(owner._lib, symbol)(*args), symbol)
     return out[0] if len(out_streams) == 1 else out
+
+
+def table_grad_layout(dims_list) -> list:
+    """mrl_table_grad_layout: where each target's slice of the table_grad_mat / table_grad_queue buffer starts, in f64 values —
+    len(dims_list) + 1 offsets, the last one the buffer's size.  ValueError for what the calls refuse: no target or more than
+    TABLE_GRAD_MAX_TARGETS, a dim below 1, more than 2^31 - 1 cells in all.  Needs no GPU."""
+    dims_list = [tuple(int(d) for d in dims) for dims in dims_list]
+    if any(len(d) != 3 or not all(-2 ** 31 <= v < 2 ** 31 for v in d) for d in dims_list):
+        raise ValueError("table_grad_layout: every target has three dims that fit an int")
+    flat = (C.c_int * max(3 * len(dims_list), 1))(*[v for d in dims_list for v in d])
+    offsets = (C.c_size_t * (TABLE_GRAD_MAX_TARGETS + 1))()
+    if load_library().mrl_table_grad_layout(flat, len(dims_list), offsets) != 0:
+        raise ValueError(f"table_grad_layout: 1..{TABLE_GRAD_MAX_TARGETS} targets of at most 2^31 - 1 cells in all, every dim >= 1")
+    return [int(v) for v in offsets[:len(dims_list) + 1]]
 
 
 class MerlHip:
@@ -773,6 +799,43 @@ class MerlHip:
                                                    _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), material, n, ptr), "mrl_table_grad_batch")
         return out
 
+    def _table_grad_targets(self, family, wi, wo, grad_rgb, targets, mat, material, out, queue=(None, None, None)):
+        """One call of include/merl_hip_fit_table.h through its row of _CALLS.  targets: the material ids whose gradients are wanted
+        (an id the library does not know: MerlHipError with ERR_MATERIAL, from mrl_material_info); out: one contiguous f64 buffer
+        that holds the targets end to end (accumulated into), or None for zeros; queue: the (queue, count, capacity) of the queue
+        form.  Returns the targets' gradients [3, *dims_k] as views of that one buffer, in the order of `targets`."""
+        targets = [int(t) for t in targets]
+        infos = [self.material_info(t) for t in targets]
+        if any(kind not in (KIND_MERL, KIND_TABLE) for kind, _ in infos):       # such a material has no planar shape to return
+            raise MerlHipError(ERR_MATERIAL, _CALLS[family, "table_grad_mat"][0], "a target is not an RGB table material")
+        shapes = [(3,) + tuple(int(d) for d in dims) for _, dims in infos]
+        offsets = table_grad_layout([sh[1:] for sh in shapes])
+        total = offsets[-1]
+        if _is_tensor(wi):
+            import torch
+            if out is None:
+                out = torch.zeros((total,), dtype=torch.float64, device=wi.device)
+            if not _is_tensor(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != total:
+                raise ValueError(f"out: need a contiguous torch.float64 tensor of {total} values (the targets end to end)")
+            ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.zeros((total,), dtype=np.float64)
+            if not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.size != total:
+                raise ValueError(f"out: need a C-contiguous numpy float64 array of {total} values (the targets end to end)")
+            ptr = out.ctypes.data
+        more = {"target_ids": (C.c_int32 * len(targets))(*targets), "n_targets": len(targets), "grad_planar": ptr}
+        _stream_call(self, family, "table_grad_mat", (wi, wo, grad_rgb), None, 3, None, mat, material, *queue, more=more)
+        flat = out.reshape(-1)
+        return tuple(flat[a:b].reshape(sh) for a, b, sh in zip(offsets, offsets[1:], shapes))
+
+    def table_grad_mat(self, wi, wo, grad_rgb, targets, mat=None, material: int = 0, out=None):
+        """G_k += A_k^T grad_rgb for every table in `targets` in one launch (mrl_table_grad_batch_mat, include/merl_hip_fit_table.h):
+        a unit adds into the target its material id names — mat[i], or `material` for all units — and into nothing if that id is
+        not among the targets.  Returns a tuple of f64 arrays [3, *dims_k], views of one buffer that holds the targets end to end;
+        numpy in -> numpy out, device tensors in -> device tensors out; out= (that one buffer, any shape) is accumulated into."""
+        return self._table_grad_targets("batch", wi, wo, grad_rgb, targets, mat, material, out)
+
     def ggx_grad(self, wi, wo, grad_rgb, material: int, curvature=None, normal: bool = False, out=None):
         """The parameter gradient of eval on a GGX material (mrl_ggx_grad_batch), parameters in the order (alpha, eta[3], k[3]):
         grad [7] += sum grad_rgb . J, and with normal=True also normal [7, 7] += sum curvature . J J^T (curvature None = 1).  f64;
@@ -901,6 +964,11 @@ class MerlHip:
     def eval_queue(self, wi, wo, queue, count, mat=None, material: int = 0, capacity=None, out=None):
         """eval() of the slots queue[0 .. min(count, capacity)); other slots of `out` stay as they are."""
         return _stream_call(self, "queue", "eval", (wi, wo), out, 3, None, mat, material, queue, count, capacity)
+
+    def table_grad_queue(self, wi, wo, grad_rgb, queue, count, targets, mat=None, material: int = 0, capacity=None, out=None):
+        """table_grad_mat() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_queue); a slot listed twice adds twice.
+        Device tensors only; the count is read on the device, so the call can be captured in a graph and replayed."""
+        return self._table_grad_targets("queue", wi, wo, grad_rgb, targets, mat, material, out, queue=(queue, count, capacity))
 
     def ggx_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
         """ggx_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_grad_dir_queue); other slots of `out` stay as they

@@ -166,6 +166,22 @@ class GpuShade:
         return self.gpu.eval_sample_queue(wi, wo, u, queue, count, mat=mat, out=self._out)
 
 
+class TableGradQueues:
+    """dL/d table over the bounce queues of a backward pass: called once per bounce with the queue that was shaded and dL/d eval
+    per slot, it adds the gradients of the tables `targets` into one buffer — one ``mrl_table_grad_queue`` launch per bounce
+    whatever the number of tables; slots of any other material add nothing.  ``grads``: one f64 tensor [3, *dims] per target."""
+
+    def __init__(self, gpu, targets):
+        self.gpu, self.targets, self.buffer, self.grads = gpu, list(targets), None, None
+
+    def __call__(self, wi, wo, grad_rgb, mat, queue, count):
+        if self.buffer is None:
+            cells = sum(math.prod(self.gpu.material_info(t)[1]) for t in self.targets)
+            self.buffer = torch.zeros(3 * cells, dtype=torch.float64, device=wi.device)
+        self.grads = self.gpu.table_grad_queue(wi, wo, grad_rgb, queue, count, self.targets, mat=mat, out=self.buffer)
+        return self.grads
+
+
 def render(shade: Callable, width: int, height: int, spp: int = 4, max_depth: int = 4, scene: Scene = None,
            device: str = "cuda:0"):
     """Path-trace the scene.  shade(wi, wo, u, mat, queue, count) -> (rgb, pdf, wo', pdf', weight') over slot arrays;

@@ -1,0 +1,503 @@
+"""mrl_table_grad_batch_mat / mrl_table_grad_queue (include/merl_hip_fit_table.h; MerlHip.table_grad_mat / table_grad_queue,
+fit.splat_mat / fit_tables): the table adjoint with a material id per unit and over wavefront queues, onto several target tables in
+one launch.  Reference: tests/table_grad_reference.py per target, on the units that carry that target's id
+(tests/table_grad_mat_inputs.py, whose inputs tests/test_table_grad_mat_cpu.py checks without a GPU).
+Bars, the project's own: per texel |G - R| <= 1e-6 S, G == 0 exactly where S == 0; "same operator" comparisons <= 1e-12 S.
+
+Measured on MI355X (worst over the cases of each test, in units of S; the order of the atomics moves the last digit):
+  one target, no ids, against mrl_table_grad_batch   1.3e-16
+  the four variants against each other, mixed ids    3.5e-16
+  queue against batch on the gathered units          2.8e-16
+  host arrays against device pointers                9e-17
+  after other calls against a fresh context          2.0e-16
+  fit_tables against fit_table                       see test_fit_tables_is_fit_table_per_table"""
+import numpy as np
+import pytest
+
+from tests import table_grad_mat_inputs as inp
+from tests import table_grad_reference as ref
+from tests.test_gpu_table_grad import SCALE, _check, _ctx, _device, _shape_table
+from tests.test_gpu_table_grad_waves import _same
+
+pytestmark = pytest.mark.gpu
+
+DIMS = (7, 5, 12)
+LOOKUPS = ((1, 0), (1, 1), (0, 0))                            # (MRL_OPT_LOOKUP, MRL_OPT_NODE)
+
+
+def _targets(gpu, specs):
+    """Shape tables for the specs, each with its own scale (inp.SCALES in turn)."""
+    return [gpu.upload_table_param(np.ones((3,) + tuple(dims)), param, inp.SCALES[k % len(inp.SCALES)]) for k, (dims, param) in enumerate(specs)]
+
+
+def _others(gpu):
+    """Ids that are no target's: another table, a GGX, a released table, -1, one past the end (taken after every upload)."""
+    other = {"table": _shape_table(gpu, (4, 3, 5)), "ggx": gpu.ggx(0.2, (0.2, 0.9, 1.1), (3.9, 2.4, 2.2))}
+    other["released"] = _shape_table(gpu, DIMS); gpu.release_material(other["released"])
+    other["negative"] = -1
+    other["out of range"] = gpu.material_count() + 7
+    return other
+
+
+def _np(views):
+    return [v.cpu().numpy() if hasattr(v, "cpu") else v for v in views]
+
+
+def _grad(gpu, wi, wo, g, targets, mat=None, material=0):
+    arrays = _device(np.array(wi), np.array(wo), np.array(g)) + ([] if mat is None else _device(np.array(mat)))
+    return _np(gpu.table_grad_mat(*arrays[:3], targets, mat=arrays[3] if mat is not None else None, material=material))
+
+
+# ---- 1. n_targets = 1, mat = NULL: the old call ----
+@pytest.mark.parametrize("lookup,node", LOOKUPS)
+def test_one_target_without_ids_is_the_single_material_call(lookup, node):
+    from tests.test_gpu_table_grad_waves import _sequence
+    wi, wo, g = _sequence(DIMS, ref.HALF_DIFF, bool(node), 1021)
+    worst = [0.0]
+    with _ctx(lookup, node) as gpu:
+        mid = _shape_table(gpu, DIMS)
+        for n in (1, 2, 63, 64, 65, 257):
+            R, S = ref.adjoint(wi[:n], wo[:n], g[:n], DIMS, trilinear=bool(lookup), center=bool(node), scale=SCALE)
+            dev = _device(np.array(wi[:n]), np.array(wo[:n]), np.array(g[:n]))
+            old = gpu.table_grad(*dev, material=mid).cpu().numpy()
+            (new,) = _np(gpu.table_grad_mat(*dev, [mid], material=mid))
+            _check(new, R, S, f"n {n} lookup {lookup} node {node}")
+            _same(new, old, S, f"n {n}: against mrl_table_grad_batch", worst)
+            # single_id that is no target: nothing is added
+            (none,) = _np(gpu.table_grad_mat(*dev, [mid], material=mid + 5))
+            assert (none == 0).all()
+    print(f"against the single-material call: worst difference {worst[0]:.3e} S")
+
+
+# ---- 2. mixed targets, stray ids, every kernel variant ----
+@pytest.mark.parametrize("lookup,node", LOOKUPS)
+def test_mixed_targets_with_stray_ids_on_every_variant(lookup, node):
+    from mitsuba_customization_amd import host
+    wi, wo, g, role = inp.interleaved(inp.MIXED, bool(node), inp.BASE)
+    refs = inp.reference(wi, wo, g, role, inp.MIXED, lookup, node)
+    between = [0.0]
+    with _ctx(lookup, node) as gpu:
+        targets = _targets(gpu, inp.MIXED)
+        mat = inp.ids_of(role, targets, _others(gpu))
+        assert len(set(mat.tolist())) == len(inp.MIXED) + len(inp.OTHERS)
+        got = []
+        for variant in (0, 1, 2, 3):
+            gpu.set_option(host.OPT_TABLE_GRAD_KERNEL, variant)
+            got.append(_grad(gpu, wi, wo, g, targets, mat))
+            for k, (R, S) in enumerate(refs):
+                _check(got[-1][k], R, S, f"n {inp.BASE} variant {variant} target {k} lookup {lookup} node {node}")
+        for v in (1, 2, 3):
+            for k, (_, S) in enumerate(refs):
+                _same(got[0][k], got[v][k], S, f"variant {v} against 0, target {k}", between)
+        print(f"variants: worst difference {between[0]:.3e} S")
+        # more than one round of the grid, the last one ragged: the sequence tiled; A^T is linear
+        n = 256 * 8 * gpu.compute_units + 37
+        q, rem = divmod(n, inp.BASE)
+        rest = inp.reference(wi[:rem], wo[:rem], g[:rem], role[:rem], inp.MIXED, lookup, node)
+        tile = lambda a: np.concatenate([np.tile(a, (q,) + (1,) * (a.ndim - 1)), a[:rem]])
+        for variant in (0, 1):
+            gpu.set_option(host.OPT_TABLE_GRAD_KERNEL, variant)
+            big = _grad(gpu, tile(wi), tile(wo), tile(g), targets, tile(mat))
+            for k, ((Rb, Sb), (Rr, Sr)) in enumerate(zip(refs, rest)):
+                _check(big[k], q * Rb + Rr, q * Sb + Sr, f"n {n} variant {variant} target {k} lookup {lookup} node {node}")
+
+
+# ---- 3. one wave on one cell, shared by two tables of the same dims ----
+@pytest.mark.parametrize("lookup,node", LOOKUPS)
+def test_same_cell_in_different_tables_is_never_summed_together(lookup, node):
+    from mitsuba_customization_amd import host
+    wi, wo = inp.one_cell_wave(bool(node))
+    dims, param = inp.SAME
+    g = np.random.default_rng(3).standard_normal((ref.WAVE, 3)).astype(np.float32)
+    kw = dict(param=param, trilinear=bool(lookup), center=bool(node))
+    with _ctx(lookup, node) as gpu:
+        a, b, quiet = (gpu.upload_table_param(np.ones((3,) + dims), param, inp.SCALES[k]) for k in range(3))
+        for name in inp.SAME_PATTERNS:
+            role = inp.same_pattern(name)
+            mat = np.where(role == 0, a, b).astype(np.int32)
+            Ra, Sa = ref.adjoint(wi[role == 0], wo[role == 0], g[role == 0], dims, scale=inp.SCALES[0], **kw)
+            Rb, Sb = ref.adjoint(wi[role == 1], wo[role == 1], g[role == 1], dims, scale=inp.SCALES[1], **kw)
+            for variant in (0, 2, 3):
+                gpu.set_option(host.OPT_TABLE_GRAD_KERNEL, variant)
+                Ga, Gq, Gb = _grad(gpu, wi, wo, g, [a, quiet, b], mat)
+                _check(Ga, Ra, Sa, f"{name} variant {variant}: table A")
+                _check(Gb, Rb, Sb, f"{name} variant {variant}: table B")
+                assert (Gq == 0).all()                              # a target no unit names
+                # B is no target: its units' share appears nowhere
+                Ga, Gq = _grad(gpu, wi, wo, g, [a, quiet], mat)
+                _check(Ga, Ra, Sa, f"{name} variant {variant}: table A alone")
+                assert (Gq == 0).all()
+
+
+# ---- 4. thin tables: the fold rules per target, cell_base at the slice borders ----
+@pytest.mark.parametrize("lookup,node", LOOKUPS)
+def test_thin_tables_fold_into_their_own_slices(lookup, node):
+    import torch
+    from mitsuba_customization_amd import host
+    n = 1536
+    wi, wo, g, role = inp.interleaved(inp.THIN, bool(node), n, quiet=(inp.THIN_QUIET,), others=False)
+    refs = inp.reference(wi, wo, g, role, inp.THIN, lookup, node)
+    total = 3 * sum(inp.cells(inp.THIN))
+    with _ctx(lookup, node) as gpu:
+        targets = _targets(gpu, inp.THIN)
+        mat = np.ascontiguousarray(np.array(targets, np.int32)[role])
+        dev = _device(np.array(wi), np.array(wo), np.array(g), mat)
+        for variant in (0, 1, 2, 3):
+            gpu.set_option(host.OPT_TABLE_GRAD_KERNEL, variant)
+            fill = np.random.default_rng(6).standard_normal(total)
+            fill[::5] = -0.0
+            out = torch.from_numpy(fill.copy()).cuda()
+            views = _np(gpu.table_grad_mat(*dev[:3], targets, mat=dev[3], out=out))
+            at = 0
+            for k, ((R, S), G) in enumerate(zip(refs, views)):
+                before = fill[at:at + R.size].reshape(R.shape); at += R.size
+                assert G.shape == R.shape
+                untouched = S == 0
+                assert np.array_equal(G[untouched].view(np.uint64), before[untouched].view(np.uint64)), (variant, k)
+                assert (np.abs(G - before - R) <= 1e-6 * S + 1e-15 * np.abs(before)).all(), (variant, k)
+                if k == inp.THIN_QUIET:
+                    assert untouched.all()                          # the neighbours' adds stop at its borders
+                else:
+                    assert (S > 0).all()
+            assert at == total
+
+
+# ---- 5. the queue form ----
+def _gathered(gpu, wi, wo, g, mat, slots, targets, material=0):
+    m = None if mat is None else np.ascontiguousarray(mat[slots])
+    return _grad(gpu, wi[slots], wo[slots], g[slots], targets, m, material)
+
+
+@pytest.mark.parametrize("lookup,node", ((1, 0), (0, 0)))
+def test_queue_form_equals_the_batch_form_on_the_gathered_units(lookup, node):
+    import torch
+    wi, wo, g, role = inp.interleaved(inp.MIXED, bool(node), inp.BASE)
+    slots = inp.queue_slots()
+    worst = [0.0]
+    with _ctx(lookup, node) as gpu:
+        targets = _targets(gpu, inp.MIXED)
+        mat = inp.ids_of(role, targets, _others(gpu))
+        # without ids every unit is single_id's, the strays too: a gradient that is poisoned in the dead rows only
+        g1 = ref.poisoned(np.random.default_rng(5).standard_normal((inp.BASE, 3)), wi, wo)
+        dwi, dwo, dg, dg1, dmat, queue = _device(np.array(wi), np.array(wo), np.array(g), g1, mat, np.array(slots))
+        count = torch.zeros(1, dtype=torch.int32, device="cuda")
+        total = 3 * sum(inp.cells(inp.MIXED))
+        for ids, material, gh, gd in ((dmat, 0, g, dg), (None, targets[0], g1, dg1)):
+            for c in (600, 5000, 1):
+                served = slots[:min(c, inp.BASE)]
+                role_q = role[served] if ids is not None else np.zeros(len(served), int)
+                refs = inp.reference(wi[served], wo[served], gh[served], role_q, inp.MIXED, lookup, node)
+                want = _gathered(gpu, wi, wo, gh, mat if ids is not None else None, served, targets, material)
+                count.fill_(c)
+                got = _np(gpu.table_grad_queue(dwi, dwo, gd, queue, count, targets, mat=ids, material=material))
+                for k, (R, S) in enumerate(refs):
+                    _check(got[k], R, S, f"queue count {c} ids {ids is not None} target {k}")
+                    _same(got[k], want[k], S, f"queue against batch, count {c} target {k}", worst)
+            # a count of 0: nothing is touched
+            fill = np.random.default_rng(9).standard_normal(total)
+            out = torch.from_numpy(fill.copy()).cuda()
+            count.fill_(0)
+            gpu.table_grad_queue(dwi, dwo, gd, queue, count, targets, mat=ids, material=material, out=out)
+            gpu.synchronize()
+            assert np.array_equal(out.cpu().numpy().view(np.uint64), fill.view(np.uint64))
+        print(f"queue against batch: worst difference {worst[0]:.3e} S")
+        # the doubled slot counts twice: the queue's first 600 against the same slots with the repeat removed
+        c = 600
+        once = np.array([s for i, s in enumerate(slots[:c]) if s not in slots[:i]])
+        assert len(once) == c - 1
+        count.fill_(c)
+        twice = _np(gpu.table_grad_queue(dwi, dwo, dg, queue, count, targets, mat=dmat))
+        single = _gathered(gpu, wi, wo, g, mat, once, targets)
+        extra = _gathered(gpu, wi, wo, g, mat, slots[3:4], targets)
+        refs = inp.reference(wi[slots[:c]], wo[slots[:c]], g[slots[:c]], role[slots[:c]], inp.MIXED, lookup, node)
+        assert role[slots[3]] < len(inp.MIXED) and ref.guard(wi[slots[3:4]], wo[slots[3:4]]).all()    # the doubled slot is a live target unit
+        for k, (_, S) in enumerate(refs):
+            _same(twice[k], single[k] + extra[k], S, f"doubled slot, target {k}", worst)
+        assert any(np.abs(e).max() > 0 for e in extra)
+        # one capture (single stream, no parallel branches), replayed with another device-side count
+        out = torch.zeros(total, dtype=torch.float64, device="cuda")
+        count.fill_(600)
+        torch.cuda.synchronize()
+        graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+        with torch.cuda.graph(graph, stream=side):
+            gpu.table_grad_queue(dwi, dwo, dg, queue, count, targets, mat=dmat, out=out)
+        out.zero_()
+        count.fill_(300)
+        graph.replay()
+        torch.cuda.synchronize()
+        direct = _np(gpu.table_grad_queue(dwi, dwo, dg, queue, count, targets, mat=dmat))
+        refs = inp.reference(wi[slots[:300]], wo[slots[:300]], g[slots[:300]], role[slots[:300]], inp.MIXED, lookup, node)
+        at, replayed = 0, out.cpu().numpy()
+        for k, (R, S) in enumerate(refs):
+            G = replayed[at:at + R.size].reshape(R.shape); at += R.size
+            _check(G, R, S, f"graph replay, target {k}")
+            _same(G, direct[k], S, f"graph replay against the direct call, target {k}", worst)
+        gpu.use_own_stream()
+
+
+# ---- 6. host arrays at chunk edges ----
+def test_host_arrays_at_chunk_edges():
+    from mitsuba_customization_amd import host
+    chunk = 512
+    wi, wo, g, role = inp.interleaved(inp.MIXED, False, inp.BASE)
+    worst = [0.0]
+    with _ctx() as gpu:
+        gpu.set_option(host.OPT_HOST_CHUNK, chunk)
+        targets = _targets(gpu, inp.MIXED)
+        mat = inp.ids_of(role, targets, _others(gpu))
+        for n in (chunk - 1, chunk, chunk + 1, inp.BASE):
+            a, b, c, m = (np.ascontiguousarray(x[:n]) for x in (wi, wo, g, mat))
+            refs = inp.reference(a, b, c, role[:n], inp.MIXED, 1, 0)
+            Gh = gpu.table_grad_mat(a, b, c, targets, mat=m)
+            assert all(isinstance(G, np.ndarray) and G.dtype == np.float64 for G in Gh)
+            Gd = _grad(gpu, a, b, c, targets, m)
+            for k, (R, S) in enumerate(refs):
+                _check(Gh[k], R, S, f"host arrays, n {n} target {k}")
+                _same(Gh[k], Gd[k], S, f"host arrays against device pointers, n {n} target {k}", worst)
+            # out= is accumulated into; without ids every unit is single_id's
+            buf = np.concatenate([G.reshape(-1) for G in Gh])
+            again = gpu.table_grad_mat(a, b, c, targets, mat=m, out=buf)
+            for k, (R, S) in enumerate(refs):
+                _check(again[k], 2 * R, 2 * S, f"host out= accumulates, n {n} target {k}")
+        g1 = ref.poisoned(np.random.default_rng(5).standard_normal((inp.BASE, 3)), wi, wo)       # the strays are target 1's units now
+        R, S = ref.adjoint(wi, wo, g1, inp.MIXED[1][0], param=inp.MIXED[1][1], scale=inp.SCALES[1])
+        alone = gpu.table_grad_mat(np.array(wi), np.array(wo), g1, targets, material=targets[1])
+        _check(alone[1], R, S, "host arrays, single_id")
+        assert (alone[0] == 0).all() and (alone[2] == 0).all()
+    print(f"host against device pointers: worst difference {worst[0]:.3e} S")
+
+
+# ---- 7. the workspace between calls of different sizes ----
+def test_workspace_is_sized_by_all_targets_and_reused():
+    big = (((33, 17, 64), ref.STANDARD_FULL),)
+    small = inp.THIN
+    wi_b, wo_b, g_b, role_b = inp.interleaved(big, False, inp.BASE, others=False)
+    wi_s, wo_s, g_s, role_s = inp.interleaved(small, False, 1536, quiet=(inp.THIN_QUIET,), others=False)
+    from tests.test_gpu_table_grad_waves import _sequence
+    wi_o, wo_o, g_o = _sequence(DIMS, ref.HALF_DIFF, False, 1021)
+
+    def calls(gpu, which):
+        out = {}
+        if "big" in which:
+            t = _targets(gpu, big)
+            out["base big"] = gpu.memory_info()["workspace_bytes"]
+            out["big"] = _grad(gpu, wi_b, wo_b, g_b, t, np.array(t, np.int32)[role_b])
+            out["bytes big"] = gpu.memory_info()["workspace_bytes"]
+        if "small" in which:
+            t = _targets(gpu, small)
+            out["base small"] = gpu.memory_info()["workspace_bytes"]
+            out["small"] = _grad(gpu, wi_s, wo_s, g_s, t, np.array(t, np.int32)[role_s])
+            out["bytes small"] = gpu.memory_info()["workspace_bytes"]
+        if "old" in which:
+            mid = _shape_table(gpu, DIMS)
+            out["old"] = [gpu.table_grad(*_device(np.array(wi_o), np.array(wo_o), np.array(g_o)), material=mid).cpu().numpy()]
+        return out
+
+    with _ctx() as gpu:
+        seq = calls(gpu, ("big", "small", "old"))
+        assert seq["bytes big"] - seq["base big"] == 33 * 17 * 64 * 256
+        assert seq["bytes small"] == seq["bytes big"]              # grow-only: the smaller call reuses it
+    with _ctx() as gpu:
+        fresh = calls(gpu, ("small",))
+        assert fresh["bytes small"] - fresh["base small"] == sum(inp.cells(small)) * 256
+    for which in ("big", "old"):
+        with _ctx() as gpu:
+            fresh.update(calls(gpu, (which,)))
+    refs = {"big": inp.reference(wi_b, wo_b, g_b, role_b, big, 1, 0), "small": inp.reference(wi_s, wo_s, g_s, role_s, small, 1, 0),
+            "old": [ref.adjoint(wi_o, wo_o, g_o, DIMS, scale=SCALE)]}
+    worst = [0.0]
+    for which in ("big", "small", "old"):
+        for k, (R, S) in enumerate(refs[which]):
+            _check(seq[which][k], R, S, f"{which} call after the others, target {k}")
+            _same(seq[which][k], fresh[which][k], S, f"{which} call against a fresh context, target {k}", worst)
+    print(f"against fresh contexts: worst difference {worst[0]:.3e} S")
+
+
+# ---- 8. status codes ----
+def test_refusals_return_their_codes_and_leave_the_buffer_alone(tmp_path):
+    import ctypes as C
+    import torch
+    from mitsuba_customization_amd import host, synth
+    n = 64
+    wi, wo, g, role = inp.interleaved((inp.SAME,), False, n, others=False)
+    wi, wo, g = np.array(wi), np.array(wo), np.array(g)
+    with _ctx(negative=1) as gpu:
+        L, ctx = gpu._lib, gpu._ctx
+        a, b = _shape_table(gpu, DIMS), _shape_table(gpu, (9, 4, 6), ref.STANDARD)
+        ggx = gpu.ggx(0.2, (0.2, 0.9, 1.1), (3.9, 2.4, 2.2))
+        nch = gpu.upload_table_nch(np.ones((5,) + DIMS))
+        gone = _shape_table(gpu, DIMS); gpu.release_material(gone)
+        rgl = gpu.upload_rgl(synth.make_rgl_fields(0))
+        spectral = gpu.upload_rgl(synth.make_rgl_fields(0, n_wavelengths=4))
+        image = str(tmp_path / "shape.image")
+        gpu.save_image(a, image)
+        restored = gpu.load_image(image)
+        mat = np.where(np.arange(n) % 2 == 0, a, b).astype(np.int32)
+        cells = 7 * 5 * 12 + 9 * 4 * 6
+        fill = np.random.default_rng(12).standard_normal(3 * cells)
+        G = fill.copy()
+        p = lambda x: None if x is None else x.ctypes.data
+        ids = lambda *t: (C.c_int32 * max(len(t), 1))(*t)
+        dwi, dwo, dg, dmat = _device(wi, wo, g, mat)
+        dG = torch.from_numpy(fill.copy()).cuda()
+        queue = torch.arange(n, dtype=torch.int32, device="cuda")
+        count = torch.tensor([n], dtype=torch.int32, device="cuda")
+        d = lambda x: None if x is None else x.data_ptr()
+
+        def batch(wi_, wo_, g_, mat_, targets, out, n_targets=None, single=0):
+            return L.mrl_table_grad_batch_mat(ctx, wi_, wo_, g_, mat_, single, n, targets, len(targets) if n_targets is None else n_targets, out)
+
+        def queued(wi_, wo_, g_, mat_, q, c, targets, out, n_targets=None, capacity=n):
+            return L.mrl_table_grad_queue(ctx, wi_, wo_, g_, mat_, 0, q, c, capacity, targets, len(targets) if n_targets is None else n_targets, out)
+        host_args, dev_args = (p(wi), p(wo), p(g), p(mat)), (d(dwi), d(dwo), d(dg), d(dmat))
+        q_args = dev_args + (d(queue), d(count))
+        good = ids(a, b)
+        # a target that is no live RGB table with its scales: MRL_ERR_MATERIAL
+        for bad in (ggx, nch, gone, rgl, spectral, restored, 99, -1):
+            assert batch(*host_args, ids(a, bad), p(G)) == -6, bad
+            assert batch(*dev_args, ids(bad, b), d(dG)) == -6, bad
+            assert queued(*q_args, ids(a, bad), d(dG)) == -6, bad
+        # the Python call gives the same status, also where no target is good
+        for targets in ([a, ggx], [gone], [99, -1], [restored]):
+            with pytest.raises(host.MerlHipError) as e:
+                gpu.table_grad_mat(dwi, dwo, dg, targets, mat=dmat)
+            assert e.value.status == host.ERR_MATERIAL, targets
+        # MRL_ERR_INVALID: a duplicate, n_targets out of range, NULL arrays
+        many = ids(*([a] * (host.TABLE_GRAD_MAX_TARGETS + 1)))
+        for call, args, out in ((batch, host_args, p(G)), (batch, dev_args, d(dG)), (queued, q_args, d(dG))):
+            assert call(*args, ids(a, b, a), out) == -1
+            assert call(*args, good, out, n_targets=0) == -1 and call(*args, good, out, n_targets=-3) == -1
+            assert call(*args, many, out, n_targets=host.TABLE_GRAD_MAX_TARGETS + 1) == -1
+            assert call(*args, None, out, n_targets=2) == -1 and call(*args, good, None) == -1
+            for k in range(3):                                       # wi, wo, grad_rgb (mat may be NULL: single_id)
+                holed = list(args); holed[k] = None
+                assert call(*holed, good, out) == -1
+        assert queued(*dev_args, None, d(count), good, d(dG)) == -1 and queued(*dev_args, d(queue), None, good, d(dG)) == -1
+        assert queued(*q_args, good, d(dG), capacity=(1 << 32) + 1) == -1
+        # pointer mixing; the queue form takes device pointers only
+        assert batch(d(dwi), p(wo), p(g), p(mat), good, p(G)) == -7
+        assert batch(*dev_args, good, p(G)) == -7 and batch(*host_args, good, d(dG)) == -7
+        assert batch(d(dwi), d(dwo), d(dg), p(mat), good, d(dG)) == -7
+        assert queued(*host_args, d(queue), d(count), good, d(dG)) == -7
+        host_queue = queue.cpu().numpy()
+        assert queued(*dev_args, host_queue.ctypes.data, d(count), good, d(dG)) == -7
+        assert queued(*q_args, good, p(G)) == -7
+        # empty calls: MRL_OK whatever the other arguments are
+        assert L.mrl_table_grad_batch_mat(ctx, None, None, None, None, 0, 0, None, 0, None) == 0
+        assert L.mrl_table_grad_queue(ctx, None, None, None, None, 0, None, None, 0, None, 0, None) == 0
+        gpu.set_option(host.OPT_NEGATIVE, 2)                        # renormalise: eval is not linear
+        assert batch(*host_args, good, p(G)) == -1 and batch(*dev_args, good, d(dG)) == -1 and queued(*q_args, good, d(dG)) == -1
+        gpu.synchronize()
+        assert np.array_equal(G, fill) and np.array_equal(dG.cpu().numpy(), fill)
+        gpu.set_option(host.OPT_NEGATIVE, 1)                        # and the context still works
+        assert batch(*dev_args, good, d(dG)) == 0 and queued(*q_args, good, d(dG)) == 0
+        gpu.synchronize()
+        Ra, Sa = ref.adjoint(wi[0::2], wo[0::2], g[0::2], DIMS, scale=SCALE)
+        got = (dG.cpu().numpy() - fill)[:Ra.size].reshape(Ra.shape)
+        assert (np.abs(got - 2 * Ra) <= 2e-6 * Sa + 1e-15 * np.abs(fill[:Ra.size].reshape(Ra.shape))).all()
+
+
+# ---- 9. fit.splat_mat, exactly ----
+def test_splat_mat_returns_the_stored_values_bit_for_bit():
+    from mitsuba_customization_amd import fit
+    specs = (((5, 4, 6), ref.HALF_DIFF), ((4, 3, 5), ref.STANDARD), ((3, 5, 8), ref.STANDARD_FULL))
+    n = 6000
+    wi, wo, _, role = inp.interleaved(specs, False, n, others=False)
+    wi, wo = np.array(wi), np.array(wo)
+    mat = np.ascontiguousarray(role, np.int32)
+    mat[5::17] = 7                                                  # units of no table
+    rng = np.random.default_rng(14)
+    truth = [(rng.random((3,) + dims) + 0.5).astype(np.float32).astype(np.float64) for dims, _ in specs]
+    params = [param for _, param in specs]
+    with _ctx(lookup=0, cosine=1) as gpu:
+        ids = [gpu.upload_table_param(t, param, (1.0, 1.0, 1.0)) for t, param in zip(truth, params)]
+        unit = fit._unit_ids(mat, ids)
+        y = gpu.eval(wi, wo, mat=unit)
+        y[mat == 7] = np.nan                                        # whatever a unit of no table measured
+        tables, masks = fit.splat_mat(gpu, [dims for dims, _ in specs], wi, wo, mat, y, params=params)
+        dev = fit.splat_mat(gpu, [dims for dims, _ in specs], *_device(wi, wo, mat, y), params=params)
+    live = ref.guard(wi, wo)
+    for k, (dims, param) in enumerate(specs):
+        at = (mat == k) & live
+        cnt, _ = ref.adjoint(wi[at], wo[at], np.ones((at.sum(), 3), np.float32), dims, param=param, trilinear=False, cosine=False)
+        assert np.array_equal(masks[k], cnt > 0) and masks[k].sum() > 0
+        assert np.array_equal(tables[k][masks[k]].view(np.uint64), truth[k][masks[k]].view(np.uint64))
+        assert (tables[k][~masks[k]] == 0).all()
+        assert np.array_equal(dev[0][k].cpu().numpy().view(np.uint64), tables[k].view(np.uint64)) and np.array_equal(dev[1][k].cpu().numpy(), masks[k])
+
+
+# ---- 10. fit.fit_tables against fit.fit_table per table ----
+FIT_SPREAD = 4.5e-16             # fit_table against itself, the largest measured (see the test's docstring)
+FIT_FACTOR = 4
+
+
+def test_fit_tables_is_fit_table_per_table(oracle):
+    """Trilinear, OPT_NEGATIVE = 1, three small tables, 5 iterations.  The two routes differ by the order of the f64 atomics alone,
+    which is also what makes fit_table differ from itself between two runs.  Distances are max |T - T'| / max |T|, the largest over
+    the three tables.  Measured on MI355X on these inputs: fit_table against itself, the single-material code path: 4.2e-16 at
+    most over all pairs of 8 runs (median 3.6e-16), 4.5e-16 in a later pair of runs: FIT_SPREAD = 4.5e-16, the largest seen;
+    fit_tables against fit_table over 6 x 8 pairs of runs: at most 5.4e-16 (median 3.6e-16).  fit_tables may differ from
+    fit_table by FIT_FACTOR = 4 times FIT_SPREAD, 1.8e-15.  fit_tables also gets 64 units of no table whose measurements are NaN,
+    which must not reach any sum, and is run on device tensors as well, under the same bound."""
+    from mitsuba_customization_amd import fit, synth
+    specs = (((6, 5, 8), ref.HALF_DIFF), ((5, 4, 6), ref.STANDARD), ((4, 6, 10), ref.STANDARD_FULL))
+    n = 1 << 15
+    wi, wo = inp.pool()
+    wi, wo = np.array(wi[:n]), np.array(wo[:n])
+    mat = (np.arange(n) % 3).astype(np.int32)
+    keep = oracle.make_opts(negative=oracle.NEGATIVE_KEEP)
+    y = np.zeros((n, 3), np.float32)
+    dims_list, params = [dims for dims, _ in specs], [param for _, param in specs]
+    for k, (dims, param) in enumerate(specs):
+        truth = synth.make_table("ggx_tab", 3 + k, dims)
+        y[mat == k] = oracle.OracleTable(truth, (1.0, 1.0, 1.0), param).eval(wi[mat == k], wo[mat == k], keep)
+    # for fit_tables only: units of no table, NaN measured
+    more = lambda a, fill: np.concatenate([a, np.full((64,) + a.shape[1:], fill, a.dtype)])
+    wi_m, wo_m, mat_m, y_m = np.concatenate([wi, wi[:64]]), np.concatenate([wo, wo[:64]]), more(mat, 7), more(y, np.nan)
+    with _ctx(negative=1) as gpu:
+        tables, res = fit.fit_tables(gpu, dims_list, wi_m, wo_m, mat_m, y_m, 5, params=params)
+        dtables, dres = fit.fit_tables(gpu, dims_list, *_device(wi_m, wo_m, mat_m, y_m), 5, params=params)
+        alone = [[fit.fit_table(gpu, dims, wi[mat == k], wo[mat == k], y[mat == k], 5, param=param) for k, (dims, param) in enumerate(specs)]
+                 for _ in range(2)]
+    spread = max(float(np.abs(alone[0][k][0] - alone[1][k][0]).max() / np.abs(alone[0][k][0]).max()) for k in range(3))
+    diff = max(float(np.abs(tables[k] - alone[0][k][0]).max() / np.abs(alone[0][k][0]).max()) for k in range(3))
+    print(f"fit_table against itself: {spread:.3e}; fit_tables against fit_table: {diff:.3e} (of max |T|)")
+    for k in range(3):
+        print(f"table {k}: residuals", " ".join(f"{r:.6e}" for r in res[k]), "| alone", " ".join(f"{r:.6e}" for r in alone[0][k][1]))
+        assert len(res[k]) == 6 and tables[k].shape == (3,) + dims_list[k] and np.isfinite(tables[k]).all()
+        assert all(b <= a * (1 + 1e-6) for a, b in zip(res[k], res[k][1:])) and res[k][-1] < res[k][0]
+    assert diff <= FIT_FACTOR * FIT_SPREAD
+    import torch
+    assert all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in dtables)
+    ddiff = max(float(np.abs(dtables[k].cpu().numpy() - alone[0][k][0]).max() / np.abs(alone[0][k][0]).max()) for k in range(3))
+    print(f"fit_tables on device tensors against fit_table: {ddiff:.3e}")
+    assert ddiff <= FIT_FACTOR * FIT_SPREAD
+    for k in range(3):
+        assert len(dres[k]) == 6 and np.isfinite(dres[k]).all() and all(b <= a * (1 + 1e-6) for a, b in zip(dres[k], dres[k][1:]))
+
+
+# ---- 11. wavefront.TableGradQueues: the bounces of a backward pass add up in one buffer ----
+def test_wavefront_helper_adds_the_bounce_queues_up():
+    import torch
+    from mitsuba_customization_amd import wavefront
+    wi, wo, g, role = inp.interleaved(inp.MIXED, False, inp.BASE)
+    slots = inp.queue_slots()
+    bounces = ((slots[:600], 600), (np.ascontiguousarray(slots[::-1]), 300))      # (queue, count) per bounce
+    worst = [0.0]
+    with _ctx() as gpu:
+        targets = _targets(gpu, inp.MIXED)
+        mat = inp.ids_of(role, targets, _others(gpu))
+        dwi, dwo, dg, dmat = _device(np.array(wi), np.array(wo), np.array(g), mat)
+        acc = wavefront.TableGradQueues(gpu, targets)
+        served = []
+        for queue, c in bounces:
+            grads = acc(dwi, dwo, dg, dmat, *_device(np.array(queue)), torch.tensor([c], dtype=torch.int32, device="cuda"))
+            served.append(queue[:c])
+        served = np.concatenate(served)
+        refs = inp.reference(wi[served], wo[served], g[served], role[served], inp.MIXED, 1, 0)
+        want = _gathered(gpu, wi, wo, g, mat, served, targets)
+        assert grads is acc.grads and len(grads) == len(targets)
+        for k, (R, S) in enumerate(refs):
+            _check(grads[k].cpu().numpy(), R, S, f"two bounces, target {k}")
+            _same(grads[k].cpu().numpy(), want[k], S, f"two bounces against one batch, target {k}", worst)
+    print(f"bounce queues against one batch: worst difference {worst[0]:.3e} S")
