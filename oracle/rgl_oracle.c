@@ -6,7 +6,8 @@
  * restates the published model from its description — the piecewise-bilinear 2-D distribution with parameter interpolation
  * ("Marginal2D" upstream), its sample / invert / eval, and the BSDF's eval / sample / pdf on top — and is pinned only by
  * self-consistency KATs (tests/test_rgl_cpu.py: invert(sample(u)) == u, densities integrate to 1, constant tables are the
- * identity warp, weight == eval / pdf, chi-square).  Only tests/, __graft_entry__.smoke() and bench.py's checker legs may use it.
+ * identity warp, weight == eval / pdf, chi-square) and by one known answer: an analytic GGX conductor tabulated in the file format
+ * comes back as its closed-form eval / pdf / weights up to the tables' discretisation error (tests/test_rgl_ggx_cpu.py).  Only tests/, __graft_entry__.smoke() and bench.py's checker legs may use it.
  *
  * Math in f64 on Float tables.  Layout of a warp with parameter dimensions (phi_i, theta_i[, channel]): slices are row-major
  * in the parameter indices; a slice is [ny][nx] nodes, x fastest.
