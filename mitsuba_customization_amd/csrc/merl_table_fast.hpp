@@ -126,7 +126,11 @@ MRL_HD Coords coords(const Vec3 &in, const Dir &out, double k_th, double k_td, d
 #pragma clang fp contract(off)
     const double sx = __builtin_fma(out.x, out.rs, in.x), sy = __builtin_fma(out.y, out.rs, in.y), sz = __builtin_fma(out.z, out.rs, in.z);
     const double ex = __builtin_fma(-out.x, out.rs, in.x), ey = __builtin_fma(-out.y, out.rs, in.y), ez = __builtin_fma(-out.z, out.rs, in.z);
-    const double rho2 = __builtin_fma(sx, sx, sy * sy);
+    // h == n.  For an exact mirror pair (wo = (-x, -y, z) of wi: what sample() returns when the lobe draws theta_h = 0) the fused
+    // s_x, s_y above are not zero but the rounding residue of in.x, in.y (1e-17): theta_h and phi_d would be read off that residue.
+    // The pair is degenerate when the ROUNDED products cancel, as they do in merl_device.hpp's in + out.
+    const bool mirror = (out.x * out.rs == -in.x) && (out.y * out.rs == -in.y);
+    const double rho2 = mirror ? 0.0 : __builtin_fma(sx, sx, sy * sy);
     const double s2 = __builtin_fma(sz, sz, rho2);
     const double e2 = __builtin_fma(ex, ex, __builtin_fma(ey, ey, ez * ez));
     // |s| > 0 for every pair that passes the cosine guards (s_z > 0); rho and |e| are zero for h == n / retro-reflection
@@ -138,7 +142,8 @@ MRL_HD Coords coords(const Vec3 &in, const Dir &out, double k_th, double k_td, d
     const bool degenerate = rho2 == 0.0;                  // h == n: phi_h = atan2(0,0) = 0
     py = degenerate ? in.y : py;
     px = degenerate ? in.x : px;
-    const double t = atan2_q1(__builtin_fabs(py), __builtin_fabs(px));
+    // wi == wo == n leaves (0, 0): atan2(0, 0) = 0 as in merl_device.hpp and the oracle (atan2_q1 alone would say pi/8)
+    const double t = (px == 0.0 && py == 0.0) ? 0.0 : atan2_q1(__builtin_fabs(py), __builtin_fabs(px));
     const double pd = ((px < 0.0) != (py < 0.0)) ? kPi - t : t;   // atan2(py,px) folded into [0,pi]
     Coords c;
     c.xh = sqrt_fast(th * k_th);                          // k_th = n_th^2 / (pi/2)

@@ -267,33 +267,17 @@ def test_product_on_the_host_at_the_edges_of_u(sparse, tmp_path_factory):
     Conditional plateaus are reached in row 0 (u0 = 0: y = 0, the row total r0 and u1 r0 exact in f64), by u1 = c / r0 rounded and
     its two Float neighbours."""
     from oracle.binding import OracleRgl
+    from tests import u_edges
     build = _host_harness(tmp_path_factory)
     tmp = tmp_path_factory.mktemp("rgl_host_edges")
     f = synth.make_rgl_fields(seed=31, n_phi=1, n_theta=1, res=(19, 11), res_ndf=8, res_sigma=6, sparse=sparse)
     orc = OracleRgl(f)
-    lum = orc.c.luminance
-    nx, ny = lum.nx, lum.ny
-    marg = np.ctypeslib.as_array(lum.marg, shape=(ny - 1,)).copy()
-    cond = np.ctypeslib.as_array(lum.cond, shape=(ny, nx - 1)).copy()
+    marg, cond = u_edges.rgl_luminance_integrals(orc)
     assert (np.diff(marg) == 0).any() if sparse == "rows" else (np.diff(cond[0]) == 0).any()      # plateaus to tie on
-    below1 = np.nextafter(np.float32(1), np.float32(0))
-    u0s = np.unique(np.concatenate([[0.0, below1, 1.0], marg, np.nextafter(marg, np.float32(0)), np.nextafter(marg, np.float32(2))])).astype(np.float32)
-    u1s = np.unique(np.concatenate([[0.0, below1, 1.0, 0.5]])).astype(np.float32)
-    pairs = [(a, b) for a in u0s for b in u1s]
-    r0 = float(cond[0, -1])                                        # (node row 0 of the "rows" file has no mass)
-    assert (r0 > 0) == (sparse == "cols")
-    if r0 > 0:
-        c_over = (cond[0].astype(np.float64) / r0).astype(np.float32)
-        for c in np.concatenate([c_over, np.nextafter(c_over, np.float32(0)), np.nextafter(c_over, np.float32(2))]):
-            pairs.append((np.float32(0), np.float32(min(c, 1.0))))
-    u = np.array(pairs, np.float32)
-    rng = np.random.default_rng(31)
-    k = 24                                                         # every u against incident directions from the normal to grazing
-    t = np.concatenate([[0.0], rng.uniform(0.0, 1.5, k - 1)]); p = rng.uniform(-np.pi, np.pi, k)
-    wis = np.stack([np.sin(t) * np.cos(p), np.sin(t) * np.sin(p), np.cos(t)], 1).astype(np.float32)
-    wi = np.repeat(wis, u.shape[0], axis=0)
-    u = np.tile(u, (k, 1))
-    wo = np.ascontiguousarray(np.roll(wi, 7, axis=0) * np.array([1, -1, 1], np.float32))
+    assert (float(cond[0, -1]) > 0) == (sparse == "cols")          # (node row 0 of the "rows" file has no mass)
+    u = u_edges.rgl_edge_pairs(marg, cond)
+    assert (u == 1).any()
+    wi, wo, u = u_edges.rgl_edge_units(u)                          # every u against incident directions from the normal to grazing
     out = _run_host(build, tmp, f, wi, wo, u)
     live = _host_matches_oracle(out, orc, wi, wo, u, 0.2, faint=1e-6)
     # and the oracle's own pdf-0 samples are the product's: a draw from a zero-mass region comes back empty on both sides
