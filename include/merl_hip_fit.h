@@ -38,8 +38,9 @@ extern "C" {
  * same inputs on the same device and options return bit-identical outputs, and grad_params has the same bits with and without
  * normal.  The workspace (256 B per block, 3 blocks per compute unit: 196 KB on 256 CUs) is kept by the context, reported by
  * mrl_memory_info as workspace and, like the other workspaces, not counted against MRL_OPT_MEMORY_LIMIT_MB.
- * Not offered: material ids per unit, queues, device groups (mrl_group_*), the one-unit paths.  The gradient with respect to the
- * directions wi, wo is mrl_ggx_grad_dir_batch / mrl_ggx_grad_dir_queue of merl_hip_diff.h. */
+ * With a material id per unit and over wavefront queues, onto several GGX materials at once: mrl_ggx_grad_batch_mat /
+ * mrl_ggx_grad_queue of merl_hip_fit_ggx.h.  Not offered: device groups (mrl_group_*), the one-unit paths.  The gradient with
+ * respect to the directions wi, wo is mrl_ggx_grad_dir_batch / mrl_ggx_grad_dir_queue of merl_hip_diff.h. */
 int mrl_ggx_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const float *curv_rgb,
                        int32_t id, size_t n, double grad_params[7], double *normal);
 

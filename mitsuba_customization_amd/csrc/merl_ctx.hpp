@@ -10,6 +10,8 @@
 //   merl_table_grad.hip    the adjoint of eval on RGB tables (mrl_table_grad_batch; with material ids and queues, onto several
 //                          tables: mrl_table_grad_batch_mat / mrl_table_grad_queue of merl_hip_fit_table.h): scatter kernels + calls
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
+//   merl_ggx_grad_mat.hip  the same with a material id per unit and over queues, onto several GGX materials in one launch
+//                          (mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue of merl_hip_fit_ggx.h): segmented reduction kernels + calls
 //   merl_dir_grad.hpp      what the direction-gradient kernels share: the grid-stride loop with its masked stores, the record a
 //                          material id names, the PER_LANE / INDEXED dispatch; their one host call is grad_dir_call of merl_calls.hip
 //   merl_ggx_dir_grad.hip  the direction gradient of eval on GGX conductors (mrl_ggx_grad_dir_batch / _queue): streaming kernel + calls
@@ -118,7 +120,9 @@ struct mrl_ctx {
     //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
     //   BUF_GRAD_BRICKS  the table-gradient calls: gradient bricks, one 256-B record per cell of every table of a call (merl_table_grad.hip)
     //   BUF_GGX_GRAD     mrl_ggx_grad_batch: one 256-B row of partial sums per block + the sums of a host-array call (merl_ggx_grad.hip)
-    enum { BUF_STAGE, BUF_QUEUES, BUF_PART_WORK, BUF_GRAD_BRICKS, BUF_GGX_GRAD, BUF_COUNT };
+    //   BUF_GGX_GRAD_MAT mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue: one 256-B row per block and target + the sums of a host-array
+    //                    call (merl_ggx_grad_mat.hip); its own buffer, so that what a captured graph points at never moves
+    enum { BUF_STAGE, BUF_QUEUES, BUF_PART_WORK, BUF_GRAD_BRICKS, BUF_GGX_GRAD, BUF_GGX_GRAD_MAT, BUF_COUNT };
     DeviceBuf buf[BUF_COUNT];
     int table_grad_kernel = 0;       // MRL_OPT_TABLE_GRAD_KERNEL
     std::vector<MaterialHost> materials;

@@ -10,6 +10,7 @@
 #include "merl_ctx.hpp"
 #include "../../include/merl_hip_fit.h"
 #include "merl_ggx_fast.hpp"
+#include "merl_ggx_grad.hpp"
 
 namespace mrl {
 
@@ -19,21 +20,8 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kBlocksPerCu = 3;           // the gradient + normal kernel holds 162 VGPRs: three waves per SIMD are resident.  One grid for both
                                          // kernels: grad_params must not depend on whether `normal` is asked for
-constexpr int kParams = 7;               // alpha, eta_r, eta_g, eta_b, k_r, k_g, k_b
-constexpr int kNormalTerms = 16;         // the unique non-zero entries of the normal matrix, in normal_entry's order
-constexpr int kRow = 32;                 // doubles per workspace row (256 B): kParams (+ kNormalTerms) used
-constexpr int kSumBlock = 1024;
+constexpr int kSumBlock = 1024;          // kParams, kNormalTerms, kRow, normal_entry, wave_sum: merl_ggx_grad.hpp
 constexpr int kSumGroups = kSumBlock / kRow;
-
-// term j of the normal matrix -> its entry (a, b), a <= b:  0: alpha.alpha;  then per channel c, three at a time:
-// alpha.eta_c, alpha.k_c, eta_c.eta_c, eta_c.k_c, k_c.k_c.  Entries that couple two channels are structurally zero.
-__host__ __device__ inline void normal_entry(int j, int &a, int &b)
-{
-    if (j == 0) { a = 0; b = 0; return; }
-    const int q = (j - 1) / 3, c = (j - 1) % 3;
-    a = q < 2 ? 0 : (q < 4 ? 1 + c : 4 + c);
-    b = (q == 0 || q == 2) ? 1 + c : 4 + c;
-}
 
 struct GgxGradArgs {
     const float *wi, *wo, *g, *h;        // h: nullptr = 1
@@ -41,14 +29,6 @@ struct GgxGradArgs {
     MaterialDev m;
     double *partials;                    // [grid][kRow]
 };
-
-// the sum over the wave in every lane, in an order that depends on nothing (xor butterfly; an f64 moves as two dwords)
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 template <bool NORMAL>
 __global__ __launch_bounds__(kBlock) void k_ggx_grad(GgxGradArgs a)

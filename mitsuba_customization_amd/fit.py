@@ -3,7 +3,8 @@ A table: the normalised splat and CGLS on |A T - y|^2, built on MerlHip.eval (A)
 numpy out, device tensors in -> device tensors out.  splat_mat / fit_tables do the same for several tables at once from one
 interleaved measurement set with a table index per unit, on MerlHip.table_grad_mat: one launch serves all tables.
 A GGX conductor (alpha, eta[3], k[3]): Levenberg-Marquardt on sum w (eval - y)^2, built on MerlHip.eval and MerlHip.ggx_grad
-(fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).
+(fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).  fit_ggx_mat / lm_ggx_mat fit several conductors at once
+from one interleaved set with a material index per unit, on MerlHip.ggx_grad_mat: one eval and one gradient launch per iteration.
 
 The context's lookup / node / cosine options define A.  fit_table uploads iterates that have negative entries, so A is linear
 only with host.OPT_NEGATIVE at keep (1), set before the context's first table is uploaded."""
@@ -247,6 +248,102 @@ def lm_ggx(eval_fn, grad_fn, rgb, start, iters, weights=None):
         history.append(loss ** 0.5)
     p, _ = _ggx_params(q)
     return float(p[0]), p[1:4].copy(), p[4:7].copy(), history
+
+
+def lm_ggx_mat(eval_fn, grad_fn, rgb, unit_ids, starts, iters, weights=None):
+    """lm_ggx() for K conductors at once from one interleaved measurement set: unit i belongs to material unit_ids[i] (an index into
+    starts; any other value: to none — what such a unit measured is never read into a sum and may be NaN).
+    eval_fn(P) -> eval [n, 3] with every unit evaluated at its own material's row of P [K, 7];  grad_fn(P, g, h) -> (sum g J [K, 7],
+    sum h J J^T [K, 7, 7]) as numpy f64, each material's sums over its own units, h None = 1; grad_fn is only called right after
+    eval_fn at the same P.  One eval_fn and at most one grad_fn call per iteration, whatever K: the normal matrix is block-diagonal,
+    so every material has its own damping and accepts or drops its own step on its own share of the loss, with lm_ggx's
+    parameterisation and k >= 0 rule.  Returns K tuples (alpha, eta [3], k [3], [sqrt(L_j) at the start and after each iteration])."""
+    count = len(starts)
+    y = _f64(rgb)
+    w = None if weights is None else _f64(weights)
+    if w is not None and w.ndim == 1:
+        w = w[:, None]
+    member = [unit_ids == j for j in range(count)]
+
+    def losses_and_model(Q):
+        ps = [_ggx_params(q) for q in Q]
+        P, S = np.stack([p for p, _ in ps]), np.stack([s for _, s in ps])
+        r = _f64(eval_fn(P)) - y
+        wr = r if w is None else w * r
+        rows = (wr * r).sum(1)
+        return np.array([float(rows[m].sum()) for m in member]), P, S, wr
+
+    def model(P, S, wr):
+        h = None if w is None else _f32(w.expand(wr.shape) if host._is_tensor(w) else np.broadcast_to(w, wr.shape))
+        g, N = grad_fn(P, _f32(wr), h)
+        g, N = np.asarray(g, np.float64), np.asarray(N, np.float64)
+        return 2.0 * S * g, 2.0 * S[:, :, None] * S[:, None, :] * N
+
+    Q = np.stack([np.concatenate([np.log(np.asarray([alpha, *eta], np.float64)), np.asarray(k, np.float64)]) for alpha, eta, k in starts])
+    loss, P, S, wr = losses_and_model(Q)
+    grad, N = model(P, S, wr)
+    lam = np.full(count, 1e-3)
+    history = [[float(v) ** 0.5] for v in loss]
+    for _ in range(iters):
+        trial = Q.copy()
+        for j in range(count):
+            d = np.diag(N[j]).copy()
+            d[d <= 0.0] = 1.0
+            try:
+                step = np.linalg.solve(N[j] + lam[j] * np.diag(d), -grad[j])
+            except np.linalg.LinAlgError:
+                step = -grad[j] / ((1.0 + lam[j]) * d)
+            trial[j] = Q[j] + step
+            trial[j, 4:] = np.maximum(trial[j, 4:], 0.1 * Q[j, 4:])
+        t_loss, t_P, t_S, t_wr = losses_and_model(trial)
+        accept = np.isfinite(t_loss) & (t_loss <= loss)
+        if accept.any():
+            # the sums at the trial point: a material that dropped its step keeps the ones of the point it stays at, and what its
+            # units hold at the trial point (NaN after an overflow) is not handed on
+            for j in range(count):
+                if not accept[j]:
+                    t_wr[member[j]] = 0.0
+            t_grad, t_N = model(t_P, t_S, t_wr)
+            Q[accept], loss[accept], grad[accept], N[accept] = trial[accept], t_loss[accept], t_grad[accept], t_N[accept]
+        lam = np.where(accept, np.maximum(lam / 10.0, 1e-12), np.minimum(lam * 10.0, 1e12))
+        for j in range(count):
+            history[j].append(float(loss[j]) ** 0.5)
+    out = []
+    for j in range(count):
+        p, _ = _ggx_params(Q[j])
+        out.append((float(p[0]), p[1:4].copy(), p[4:7].copy(), history[j]))
+    return out
+
+
+def fit_ggx_mat(ctx, wi, wo, mat, rgb, starts, iters, weights=None):
+    """fit_ggx() for K conductors from one interleaved measurement set: mat[i] (int32) is the index into starts of the material unit
+    i measured; any other value: none.  Every iteration creates the K materials, runs one eval with material ids and one
+    ggx_grad_mat(..., normal=True) on them, and releases them.  Returns K tuples (alpha, eta [3], k [3], residual history) — see
+    lm_ggx_mat."""
+    held = []
+    unit = [None]
+
+    def drop():
+        while held:
+            ctx.release_material(held.pop())
+
+    def eval_fn(P):
+        drop()
+        for p in P:
+            held.append(ctx.ggx(float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]]))
+        unit[0] = _unit_ids(mat, held)
+        return ctx.eval(wi, wo, mat=unit[0])
+
+    def grad_fn(P, g, h):
+        grad, N = ctx.ggx_grad_mat(wi, wo, g, held, mat=unit[0], curvature=h, normal=True)
+        if host._is_tensor(grad):
+            grad, N = grad.cpu().numpy(), N.cpu().numpy()
+        return grad, N
+
+    try:
+        return lm_ggx_mat(eval_fn, grad_fn, rgb, mat, starts, iters, weights)
+    finally:
+        drop()
 
 
 def fit_ggx(ctx, wi, wo, rgb, start, iters, weights=None):

@@ -77,6 +77,9 @@ DIFF_NCH_ABI_SYMBOLS = ("mrl_table_grad_dir_batch_nch", "mrl_table_grad_dir_queu
 # every symbol include/merl_hip_fit_table.h declares: the table adjoint with a material id per unit and over wavefront queues
 FIT_TABLE_ABI_SYMBOLS = ("mrl_table_grad_batch_mat", "mrl_table_grad_queue", "mrl_table_grad_layout")
 TABLE_GRAD_MAX_TARGETS = 16         # MRL_TABLE_GRAD_MAX_TARGETS
+# every symbol include/merl_hip_fit_ggx.h declares: the GGX parameter gradient with a material id per unit and over wavefront queues
+FIT_GGX_ABI_SYMBOLS = ("mrl_ggx_grad_batch_mat", "mrl_ggx_grad_queue")
+GGX_GRAD_MAX_TARGETS = 16           # MRL_GGX_GRAD_MAX_TARGETS
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -229,6 +232,12 @@ _CALLS = {(family, mode): (symbol.format(mode), middle) + streams
 _TARGETS = ("target_ids", "n_targets", "grad_planar")
 _CALLS["batch", "table_grad_mat"] = ("mrl_table_grad_batch_mat", _FAMILIES["batch"][1] + _TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
 _CALLS["queue", "table_grad_mat"] = ("mrl_table_grad_queue", _FAMILIES["queue"][1] + _TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
+# the GGX parameter gradient with targets (include/merl_hip_fit_ggx.h): a fourth input stream, curv_rgb (may be None), and the two
+# arrays the calls add into as middle parameters
+_GGX_TARGETS = ("target_ids", "n_targets", "grad_params", "normal")
+_GGX_GRAD_INS = (_WI, _WO, ("grad_rgb", 3), ("curv_rgb", 3))
+_CALLS["batch", "ggx_grad_mat"] = ("mrl_ggx_grad_batch_mat", _FAMILIES["batch"][1] + _GGX_TARGETS, _GGX_GRAD_INS, ())
+_CALLS["queue", "ggx_grad_mat"] = ("mrl_ggx_grad_queue", _FAMILIES["queue"][1] + _GGX_TARGETS, _GGX_GRAD_INS, ())
 
 
 _lib = None
@@ -866,6 +875,43 @@ class MerlHip:
                                                  material, n, ptrs[0], ptrs[1] if normal else None), "mrl_ggx_grad_batch")
         return outs if normal else outs[0]
 
+    def _ggx_grad_targets(self, family, wi, wo, grad_rgb, targets, mat, material, curvature, normal, out, queue=(None, None, None)):
+        """One call of include/merl_hip_fit_ggx.h through its row of _CALLS.  targets: the GGX material ids whose gradients are
+        wanted; out: grad [T, 7], or (grad, normal [T, 7, 7]) with normal=True, f64, accumulated into (None: zeros); queue: the
+        (queue, count, capacity) of the queue form.  Returns grad, or (grad, normal)."""
+        targets = [int(t) for t in targets]
+        count = len(targets)
+        outs = () if out is None else ((out,) if not normal else tuple(out))
+        if out is not None and len(outs) != (2 if normal else 1):
+            raise ValueError("out: need grad, or (grad, normal) with normal=True")
+        shapes = ((count, 7), (count, 7, 7))[:2 if normal else 1]
+        if _is_tensor(wi):
+            import torch
+            if out is None:
+                outs = tuple(torch.zeros(s, dtype=torch.float64, device=wi.device) for s in shapes)
+            for o, s in zip(outs, shapes):
+                if not _is_tensor(o) or o.dtype != torch.float64 or not o.is_contiguous() or tuple(o.shape) != s:
+                    raise ValueError(f"out: need a contiguous torch.float64 tensor of shape {s}")
+            ptrs = [o.data_ptr() for o in outs]
+        else:
+            if out is None:
+                outs = tuple(np.zeros(s, dtype=np.float64) for s in shapes)
+            for o, s in zip(outs, shapes):
+                if not isinstance(o, np.ndarray) or o.dtype != np.float64 or not o.flags["C_CONTIGUOUS"] or o.shape != s:
+                    raise ValueError(f"out: need a C-contiguous numpy float64 array of shape {s}")
+            ptrs = [o.ctypes.data for o in outs]
+        more = {"target_ids": (C.c_int32 * max(count, 1))(*targets), "n_targets": count, "grad_params": ptrs[0],
+                "normal": ptrs[1] if normal else None}
+        _stream_call(self, family, "ggx_grad_mat", (wi, wo, grad_rgb, curvature), None, 3, None, mat, material, *queue, more=more)
+        return outs if normal else outs[0]
+
+    def ggx_grad_mat(self, wi, wo, grad_rgb, targets, mat=None, material: int = 0, curvature=None, normal: bool = False, out=None):
+        """ggx_grad() for every GGX material in `targets` in one launch (mrl_ggx_grad_batch_mat, include/merl_hip_fit_ggx.h): a unit
+        adds into the target its material id names — mat[i], or `material` for all units — with the Jacobian taken at that
+        material's parameters, and into nothing if that id is not among the targets.  Returns grad [T, 7], or with normal=True
+        (grad, normal [T, 7, 7]), f64; numpy in -> numpy out, device tensors in -> device tensors out; out= is accumulated into."""
+        return self._ggx_grad_targets("batch", wi, wo, grad_rgb, targets, mat, material, curvature, normal, out)
+
     def _grad_dir_outputs(self, wi, want, out, alloc):
         """(grad_wi or None, grad_wo or None) for `want`, a subset of ("wi", "wo") in that order: taken from out= (one array, or a
         tuple in want's order) or allocated."""
@@ -969,6 +1015,12 @@ class MerlHip:
         """table_grad_mat() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_queue); a slot listed twice adds twice.
         Device tensors only; the count is read on the device, so the call can be captured in a graph and replayed."""
         return self._table_grad_targets("queue", wi, wo, grad_rgb, targets, mat, material, out, queue=(queue, count, capacity))
+
+    def ggx_grad_queue(self, wi, wo, grad_rgb, queue, count, targets, mat=None, material: int = 0, capacity=None, curvature=None,
+                       normal: bool = False, out=None):
+        """ggx_grad_mat() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_grad_queue); a slot listed twice adds twice.
+        Device tensors only; the count is read on the device, so the call can be captured in a graph and replayed."""
+        return self._ggx_grad_targets("queue", wi, wo, grad_rgb, targets, mat, material, curvature, normal, out, queue=(queue, count, capacity))
 
     def ggx_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
         """ggx_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_grad_dir_queue); other slots of `out` stay as they
