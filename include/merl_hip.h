@@ -524,7 +524,8 @@ size_t mrl_rgl_route(int mode, int spectral, int ids, int queued, int search, si
  * the staging and queue buffers it is not counted against MRL_OPT_MEMORY_LIMIT_MB; an allocation that fails is MRL_ERR_OOM.  A
  * host-pointer call also holds a device copy of grad_planar (24 B per cell) for its duration.
  * Material ids per unit and wavefront queues, onto several target tables in one launch: mrl_table_grad_batch_mat /
- * mrl_table_grad_queue of merl_hip_fit_table.h.  Not offered: n-channel tables, device groups, the one-unit host path. */
+ * mrl_table_grad_queue of merl_hip_fit_table.h.  n-channel tables: merl_hip_fit_nch.h.  Not offered: device groups, the one-unit
+ * host path. */
 int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                          int32_t id, size_t n, double *grad_planar);
 

@@ -56,7 +56,7 @@ extern "C" {
  * alone — the whole-array, material-id, queue and host-array forms return identical bits for the same unit, whatever n, the grid
  * or the unit's position; grad_wi has the same bits with and without grad_wo.
  * Not offered: RGL and spectral RGL tables, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf
- * and sample, the renormalising blend (MRL_OPT_NEGATIVE = 2), the adjoint in an n-channel table's texels. */
+ * and sample, the renormalising blend (MRL_OPT_NEGATIVE = 2).  The adjoint in an n-channel table's texels: merl_hip_fit_nch.h. */
 int mrl_table_grad_dir_batch_nch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_values,
                                  const int32_t *mat, int32_t single_id, size_t n, int n_channels,
                                  float *grad_wi, float *grad_wo);

@@ -9,6 +9,8 @@
 //   merl_rgl_spectral.hip  spectral RGL materials: constructor + calls
 //   merl_table_grad.hip    the adjoint of eval on RGB tables (mrl_table_grad_batch; with material ids and queues, onto several
 //                          tables: mrl_table_grad_batch_mat / mrl_table_grad_queue of merl_hip_fit_table.h): scatter kernels + calls
+//   merl_table_grad_nch.hip  the same adjoint on n-channel tables (mrl_table_grad_batch_nch / mrl_table_grad_queue_nch of
+//                          merl_hip_fit_nch.h): scatter kernels per (cell, channel group of 4) + calls
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
 //   merl_ggx_grad_mat.hip  the same with a material id per unit and over queues, onto several GGX materials in one launch
 //                          (mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue of merl_hip_fit_ggx.h): segmented reduction kernels + calls
@@ -64,6 +66,9 @@ struct MaterialHost {
     // mrl_table_grad_batch needs them; a table restored from an image file does not carry them (has_scale stays false)
     double scale[3] = { 1.0, 1.0, 1.0 };
     bool has_scale = false;
+    // n-channel tables uploaded as planar arrays: their n_ch channel scales (all ones when the caller passed none), which the
+    // n-channel table adjoint needs (merl_table_grad_nch.hip); empty for every other material and for one restored from an image file
+    std::vector<double> nch_scale;
 };
 
 // a device buffer that only grows
@@ -118,7 +123,8 @@ struct mrl_ctx {
     //   BUF_STAGE        one slot of a staged host-array call (slot_layout)
     //   BUF_QUEUES       kind-partitioned mixed batches: [2][n] unit indices + partition work area behind them
     //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
-    //   BUF_GRAD_BRICKS  the table-gradient calls: gradient bricks, one 256-B record per cell of every table of a call (merl_table_grad.hip)
+    //   BUF_GRAD_BRICKS  the table-gradient calls: gradient bricks, one 256-B record per cell of every table of a call (merl_table_grad.hip),
+    //                    per cell and channel group of 4 for n-channel tables (merl_table_grad_nch.hip)
     //   BUF_GGX_GRAD     mrl_ggx_grad_batch: one 256-B row of partial sums per block + the sums of a host-array call (merl_ggx_grad.hip)
     //   BUF_GGX_GRAD_MAT mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue: one 256-B row per block and target + the sums of a host-array
     //                    call (merl_ggx_grad_mat.hip); its own buffer, so that what a captured graph points at never moves

@@ -268,6 +268,8 @@ int upload_table_nch(mrl_ctx *ctx, const double *planar, const int dims[3], int 
     m.dev.layout = mrl::LAYOUT_BRICK;
     m.dev.n_ch = n_ch;
     m.dev.param = ctx->table_param;
+    try { m.nch_scale.assign(scale, scale + n_ch); }
+    catch (const std::bad_alloc &) { (void)hipFree(m.d_texels); (void)hipFree(m.d_sampling); return fail(ctx, MRL_ERR_OOM, "channel scales"); }
     rc = place_material(ctx, m, out_id);
     if (rc != MRL_OK) { (void)hipFree(m.d_texels); (void)hipFree(m.d_sampling); return rc; }
     return MRL_OK;

@@ -1,7 +1,9 @@
 """From measurements (wi, wo, rgb) to a material.
 A table: the normalised splat and CGLS on |A T - y|^2, built on MerlHip.eval (A) and MerlHip.table_grad (A^T).  numpy arrays in ->
 numpy out, device tensors in -> device tensors out.  splat_mat / fit_tables do the same for several tables at once from one
-interleaved measurement set with a table index per unit, on MerlHip.table_grad_mat: one launch serves all tables.
+interleaved measurement set with a table index per unit, on MerlHip.table_grad_mat: one launch serves all tables.  splat_nch /
+fit_table_nch are the twins for an n-channel table (1..32 channels, spectral measurements), on MerlHip.eval_nch and
+MerlHip.table_grad_nch: one launch serves all channels.
 A GGX conductor (alpha, eta[3], k[3]): Levenberg-Marquardt on sum w (eval - y)^2, built on MerlHip.eval and MerlHip.ggx_grad
 (fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).  fit_ggx_mat / lm_ggx_mat fit several conductors at once
 from one interleaved set with a material index per unit, on MerlHip.ggx_grad_mat: one eval and one gradient launch per iteration.
@@ -45,6 +47,29 @@ def splat(ctx, dims, wi, wo, rgb, param=None, scale=(1.0, 1.0, 1.0)):
     return num / (den + ~mask) * mask, mask
 
 
+def _cgls(A, At, y, x, iters):
+    """CGLS on |A x - y|^2 from the start x.  Returns (x, [|A x_k - y| for k = 0 .. iters])."""
+    r = y - A(x)
+    s = At(r)
+    p, gamma = s, _dot(s, s)
+    residuals = [_dot(r, r) ** 0.5]
+    for _ in range(iters):
+        q = A(p)
+        qq = _dot(q, q)
+        if gamma == 0.0 or qq == 0.0:
+            residuals.append(residuals[-1])
+            continue
+        alpha = gamma / qq
+        x = x + alpha * p
+        r = r - alpha * q
+        s = At(r)
+        gamma_new = _dot(s, s)
+        p = s + (gamma_new / gamma) * p
+        gamma = gamma_new
+        residuals.append(_dot(r, r) ** 0.5)
+    return x, residuals
+
+
 def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
     """CGLS on |A T - y|^2 started from the splat.  Returns (table f64 [3, *dims], [|A T_k - y| for k = 0 .. iters])."""
     if ctx.get_option(host.OPT_NEGATIVE) != 1:
@@ -64,27 +89,55 @@ def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
         return ctx.table_grad(wi, wo, _f32(r), material=shape_mid)
 
     try:
-        r = y - A(x)
-        s = At(r)
-        p, gamma = s, _dot(s, s)
-        residuals = [_dot(r, r) ** 0.5]
-        for _ in range(iters):
-            q = A(p)
-            qq = _dot(q, q)
-            if gamma == 0.0 or qq == 0.0:
-                residuals.append(residuals[-1])
-                continue
-            alpha = gamma / qq
-            x = x + alpha * p
-            r = r - alpha * q
-            s = At(r)
-            gamma_new = _dot(s, s)
-            p = s + (gamma_new / gamma) * p
-            gamma = gamma_new
-            residuals.append(_dot(r, r) ** 0.5)
+        return _cgls(A, At, y, x, iters)
     finally:
         ctx.release_material(shape_mid)
-    return x, residuals
+
+
+# ---- n-channel tables (1..32 channels: MerlHip.eval_nch is A, MerlHip.table_grad_nch is A^T; one launch serves all channels) ----
+def _upload_nch(ctx, table, param, scale) -> int:
+    t = table.cpu().numpy() if host._is_tensor(table) else table
+    return ctx.upload_table_nch(t, scale) if param is None else ctx.upload_table_param(t, param, scale)
+
+
+def splat_nch(ctx, dims, wi, wo, values, param=None, scale=None):
+    """splat() for an n-channel table: values is [n, n_channels], the channel count is its second dim.  Returns (table f64
+    [n_channels, *dims], mask of the cells some unit reached); the rest is 0."""
+    n_ch = int(values.shape[1])
+    mid = _upload_nch(ctx, np.ones((n_ch,) + tuple(dims)), param, scale)
+    try:
+        (num,) = ctx.table_grad_nch(wi, wo, _f32(values), n_ch, [mid], material=mid)
+        (den,) = ctx.table_grad_nch(wi, wo, ctx.eval_nch(wi, wo, n_ch, material=mid), n_ch, [mid], material=mid)
+    finally:
+        ctx.release_material(mid)
+    mask = den > 0
+    return num / (den + ~mask) * mask, mask
+
+
+def fit_table_nch(ctx, dims, wi, wo, values, iters, param=None, scale=None):
+    """fit_table() for an n-channel table: CGLS on |A T - y|^2 started from splat_nch.  Returns (table f64 [n_channels, *dims],
+    [|A T_k - y| for k = 0 .. iters])."""
+    if ctx.get_option(host.OPT_NEGATIVE) != 1:
+        raise ValueError("fit_table_nch needs OPT_NEGATIVE = 1 (keep): the iterates have negative entries and a clamped upload is not linear")
+    n_ch = int(values.shape[1])
+    y = _f64(values)
+    x, _ = splat_nch(ctx, dims, wi, wo, values, param, scale)
+    shape_mid = _upload_nch(ctx, np.ones((n_ch,) + tuple(dims)), param, scale)   # what table_grad_nch takes dims, parameterisation and scales from
+
+    def A(table):
+        mid = _upload_nch(ctx, table, param, scale)
+        try:
+            return _f64(ctx.eval_nch(wi, wo, n_ch, material=mid))
+        finally:
+            ctx.release_material(mid)
+
+    def At(r):
+        return ctx.table_grad_nch(wi, wo, _f32(r), n_ch, [shape_mid], material=shape_mid)[0]
+
+    try:
+        return _cgls(A, At, y, x, iters)
+    finally:
+        ctx.release_material(shape_mid)
 
 
 # ---- several tables from one interleaved measurement set (MerlHip.table_grad_mat: one launch for all tables) ----

@@ -77,6 +77,8 @@ DIFF_NCH_ABI_SYMBOLS = ("mrl_table_grad_dir_batch_nch", "mrl_table_grad_dir_queu
 # every symbol include/merl_hip_fit_table.h declares: the table adjoint with a material id per unit and over wavefront queues
 FIT_TABLE_ABI_SYMBOLS = ("mrl_table_grad_batch_mat", "mrl_table_grad_queue", "mrl_table_grad_layout")
 TABLE_GRAD_MAX_TARGETS = 16         # MRL_TABLE_GRAD_MAX_TARGETS
+# every symbol include/merl_hip_fit_nch.h declares: the same adjoint on n-channel table materials
+FIT_NCH_ABI_SYMBOLS = ("mrl_table_grad_batch_nch", "mrl_table_grad_queue_nch", "mrl_table_grad_layout_nch")
 # every symbol include/merl_hip_fit_ggx.h declares: the GGX parameter gradient with a material id per unit and over wavefront queues
 FIT_GGX_ABI_SYMBOLS = ("mrl_ggx_grad_batch_mat", "mrl_ggx_grad_queue")
 GGX_GRAD_MAX_TARGETS = 16           # MRL_GGX_GRAD_MAX_TARGETS
@@ -232,6 +234,9 @@ _CALLS = {(family, mode): (symbol.format(mode), middle) + streams
 _TARGETS = ("target_ids", "n_targets", "grad_planar")
 _CALLS["batch", "table_grad_mat"] = ("mrl_table_grad_batch_mat", _FAMILIES["batch"][1] + _TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
 _CALLS["queue", "table_grad_mat"] = ("mrl_table_grad_queue", _FAMILIES["queue"][1] + _TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
+# the same on n-channel tables (include/merl_hip_fit_nch.h): grad_values is [n, n_channels]
+_CALLS["batch", "table_grad_nch"] = ("mrl_table_grad_batch_nch", _FAMILIES["batch_nch"][1] + _TARGETS, (_WI, _WO, ("grad_values", 0)), ())
+_CALLS["queue", "table_grad_nch"] = ("mrl_table_grad_queue_nch", _FAMILIES["queue_nch"][1] + _TARGETS, (_WI, _WO, ("grad_values", 0)), ())
 # the GGX parameter gradient with targets (include/merl_hip_fit_ggx.h): a fourth input stream, curv_rgb (may be None), and the two
 # arrays the calls add into as middle parameters
 _GGX_TARGETS = ("target_ids", "n_targets", "grad_params", "normal")
@@ -291,6 +296,7 @@ def load_library(path: Optional[str] = None):
     L.mrl_partition_by_material.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
     L.mrl_table_grad_layout.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_size_t)]
+    L.mrl_table_grad_layout_nch.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     L.mrl_ggx_grad_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int32, C.c_size_t, vp, vp]
     L.mrl_ggx_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
@@ -436,7 +442,7 @@ def _stream_call(owner, family, mode, ins, out=None, width=3, wavelengths=None, 
         between.update(queue=q, queue_count=q_count, capacity=cap)
     between.update(more or {})                          # middle parameters only some rows have
     args = [owner._g if family == "group" else owner._ctx]
-    args += [_addr(x, np.float32, cols, n, name) for (name, cols), x in zip(in_streams, ins)]
+    args += [_addr(x, np.float32, width if cols == 0 else cols, n, name) for (name, cols), x in zip(in_streams, ins)]
     args += [between[name] for name in middle]
     args += [_addr(x, np.float32, width if cols == 0 else cols, n, name) for (name, cols), x in zip(out_streams, out)]
     owner._check(getattr(owner._lib, symbol)(*args), symbol)
@@ -454,6 +460,21 @@ def table_grad_layout(dims_list) -> list:
     offsets = (C.c_size_t * (TABLE_GRAD_MAX_TARGETS + 1))()
     if load_library().mrl_table_grad_layout(flat, len(dims_list), offsets) != 0:
         raise ValueError(f"table_grad_layout: 1..{TABLE_GRAD_MAX_TARGETS} targets of at most 2^31 - 1 cells in all, every dim >= 1")
+    return [int(v) for v in offsets[:len(dims_list) + 1]]
+
+
+def table_grad_layout_nch(dims_list, n_channels: int) -> list:
+    """mrl_table_grad_layout_nch: table_grad_layout() for the table_grad_nch / table_grad_queue_nch buffer — offsets in f64 values,
+    n_channels times the cells before a target.  ValueError for what the calls refuse: what table_grad_layout refuses, n_channels
+    outside 1..32, more than 2^31 - 1 gradient bricks (cells x ceil(n_channels / 4)) in all.  Needs no GPU."""
+    dims_list = [tuple(int(d) for d in dims) for dims in dims_list]
+    if any(len(d) != 3 or not all(-2 ** 31 <= v < 2 ** 31 for v in d) for d in dims_list):
+        raise ValueError("table_grad_layout_nch: every target has three dims that fit an int")
+    flat = (C.c_int * max(3 * len(dims_list), 1))(*[v for d in dims_list for v in d])
+    offsets = (C.c_size_t * (TABLE_GRAD_MAX_TARGETS + 1))()
+    if load_library().mrl_table_grad_layout_nch(flat, len(dims_list), int(n_channels), offsets) != 0:
+        raise ValueError(f"table_grad_layout_nch: 1..{TABLE_GRAD_MAX_TARGETS} targets, every dim >= 1, 1..32 channels, "
+                         "at most 2^31 - 1 cells x ceil(n_channels / 4) in all")
     return [int(v) for v in offsets[:len(dims_list) + 1]]
 
 
@@ -808,17 +829,25 @@ class MerlHip:
                                                    _addr(grad_rgb, np.float32, 3, n, "grad_rgb"), material, n, ptr), "mrl_table_grad_batch")
         return out
 
-    def _table_grad_targets(self, family, wi, wo, grad_rgb, targets, mat, material, out, queue=(None, None, None)):
-        """One call of include/merl_hip_fit_table.h through its row of _CALLS.  targets: the material ids whose gradients are wanted
-        (an id the library does not know: MerlHipError with ERR_MATERIAL, from mrl_material_info); out: one contiguous f64 buffer
-        that holds the targets end to end (accumulated into), or None for zeros; queue: the (queue, count, capacity) of the queue
-        form.  Returns the targets' gradients [3, *dims_k] as views of that one buffer, in the order of `targets`."""
+    def _table_grad_targets(self, family, wi, wo, grad_rgb, targets, mat, material, out, queue=(None, None, None), n_channels=None):
+        """One call of include/merl_hip_fit_table.h — with n_channels: of include/merl_hip_fit_nch.h — through its row of _CALLS.
+        targets: the material ids whose gradients are wanted (an id the library does not know: MerlHipError with ERR_MATERIAL, from
+        mrl_material_info); out: one contiguous f64 buffer that holds the targets end to end (accumulated into), or None for zeros;
+        queue: the (queue, count, capacity) of the queue form.  Returns the targets' gradients [3, *dims_k] ([n_channels, *dims_k])
+        as views of that one buffer, in the order of `targets`."""
         targets = [int(t) for t in targets]
         infos = [self.material_info(t) for t in targets]
-        if any(kind not in (KIND_MERL, KIND_TABLE) for kind, _ in infos):       # such a material has no planar shape to return
-            raise MerlHipError(ERR_MATERIAL, _CALLS[family, "table_grad_mat"][0], "a target is not an RGB table material")
-        shapes = [(3,) + tuple(int(d) for d in dims) for _, dims in infos]
-        offsets = table_grad_layout([sh[1:] for sh in shapes])
+        mode, width = ("table_grad_mat", 3) if n_channels is None else ("table_grad_nch", int(n_channels))
+        if n_channels is None or width == 3:
+            if any(kind not in (KIND_MERL, KIND_TABLE) for kind, _ in infos):   # such a material has no planar shape to return
+                raise MerlHipError(ERR_MATERIAL, _CALLS[family, mode][0], "a target is not an RGB table material")
+        elif not 1 <= width <= 32:
+            raise MerlHipError(ERR_INVALID, _CALLS[family, mode][0], "channel count must be 1..32")
+        elif any(kind != KIND_TABLE_NCH or self.material_channels(t) != width for t, (kind, _) in zip(targets, infos)):
+            raise MerlHipError(ERR_MATERIAL, _CALLS[family, mode][0], f"a target is not an n-channel table of {width} channels")
+        shapes = [(width,) + tuple(int(d) for d in dims) for _, dims in infos]
+        dims_list = [sh[1:] for sh in shapes]
+        offsets = table_grad_layout(dims_list) if n_channels is None else table_grad_layout_nch(dims_list, width)
         total = offsets[-1]
         if _is_tensor(wi):
             import torch
@@ -834,9 +863,16 @@ class MerlHip:
                 raise ValueError(f"out: need a C-contiguous numpy float64 array of {total} values (the targets end to end)")
             ptr = out.ctypes.data
         more = {"target_ids": (C.c_int32 * len(targets))(*targets), "n_targets": len(targets), "grad_planar": ptr}
-        _stream_call(self, family, "table_grad_mat", (wi, wo, grad_rgb), None, 3, None, mat, material, *queue, more=more)
+        _stream_call(self, family, mode, (wi, wo, grad_rgb), None, width, None, mat, material, *queue, more=more)
         flat = out.reshape(-1)
         return tuple(flat[a:b].reshape(sh) for a, b, sh in zip(offsets, offsets[1:], shapes))
+
+    def table_grad_nch(self, wi, wo, grad_values, n_channels: int, targets, mat=None, material: int = 0, out=None):
+        """G_k += A_k^T grad_values for every n-channel table in `targets` in one launch (mrl_table_grad_batch_nch,
+        include/merl_hip_fit_nch.h): table_grad_mat() with grad_values [n, n_channels] and targets of exactly n_channels channels
+        (3: RGB tables).  Returns a tuple of f64 arrays [n_channels, *dims_k], views of one buffer that holds the targets end to end;
+        numpy in -> numpy out, device tensors in -> device tensors out; out= (that one buffer, any shape) is accumulated into."""
+        return self._table_grad_targets("batch", wi, wo, grad_values, targets, mat, material, out, n_channels=n_channels)
 
     def table_grad_mat(self, wi, wo, grad_rgb, targets, mat=None, material: int = 0, out=None):
         """G_k += A_k^T grad_rgb for every table in `targets` in one launch (mrl_table_grad_batch_mat, include/merl_hip_fit_table.h):
@@ -1015,6 +1051,13 @@ class MerlHip:
         """table_grad_mat() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_queue); a slot listed twice adds twice.
         Device tensors only; the count is read on the device, so the call can be captured in a graph and replayed."""
         return self._table_grad_targets("queue", wi, wo, grad_rgb, targets, mat, material, out, queue=(queue, count, capacity))
+
+    def table_grad_queue_nch(self, wi, wo, grad_values, queue, count, n_channels: int, targets, mat=None, material: int = 0, capacity=None,
+                             out=None):
+        """table_grad_nch() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_queue_nch); a slot listed twice adds twice.
+        GPU tensors only; capturable in a HIP graph after one call outside the capture (the workspace then has its size)."""
+        return self._table_grad_targets("queue", wi, wo, grad_values, targets, mat, material, out, queue=(queue, count, capacity),
+                                        n_channels=n_channels)
 
     def ggx_grad_queue(self, wi, wo, grad_rgb, queue, count, targets, mat=None, material: int = 0, capacity=None, curvature=None,
                        normal: bool = False, out=None):
