@@ -56,7 +56,8 @@ extern "C" {
  * Workspace: grid x n_targets rows of 256 B, kept by the context in a buffer of its own (mrl_ggx_grad_batch keeps its workspace:
  * what a graph captured from either call points at stays valid), sized once for 16 targets; mrl_memory_info reports it as
  * workspace, and it is not counted against MRL_OPT_MEMORY_LIMIT_MB; if it does not fit: MRL_ERR_OOM.
- * Not offered: device groups (mrl_group_*), the one-unit paths, an autograd wrapper for the parameters. */
+ * Not offered: device groups (mrl_group_*), the one-unit paths.  (An autograd wrapper for the parameters: diff.ggx_eval(params=),
+ * over mrl_material_update_ggx of merl_hip_update.h.) */
 int mrl_ggx_grad_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const float *curv_rgb,
                            const int32_t *mat, int32_t single_id, size_t n,
                            const int32_t *target_ids, int n_targets, double *grad_params, double *normal);

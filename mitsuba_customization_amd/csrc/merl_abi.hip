@@ -369,7 +369,7 @@ int mrl_destroy(mrl_ctx *ctx)
         if (ctx->scalar_dev.b) (void)hipHostFree(ctx->scalar_dev.b);
     }
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto &m : ctx->materials) { if (m.d_texels && !m.in_arena) (void)hipFree(m.d_texels); if (m.d_sampling) (void)hipFree(m.d_sampling); if (m.d_sampling2d) (void)hipFree(m.d_sampling2d); }
+    for (auto &m : ctx->materials) { if (m.d_texels && !m.in_arena) (void)hipFree(m.d_texels); if (m.d_sampling) (void)hipFree(m.d_sampling); if (m.d_sampling2d) (void)hipFree(m.d_sampling2d); if (m.update_ws.p) (void)hipFree(m.update_ws.p); }
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->d_materials) (void)hipFree(ctx->d_materials);
     if (ctx->d_dummy) (void)hipFree(ctx->d_dummy);
@@ -539,6 +539,7 @@ int mrl_memory_info(const mrl_ctx *ctx, size_t *material_bytes, size_t *workspac
         *workspace_bytes = (ctx->arena_bytes > ctx->arena_used ? ctx->arena_bytes - ctx->arena_used : 0) + ctx->d_materials_cap * sizeof(mrl::MaterialDev) +
                            (ctx->d_dummy ? 256 + 5 * sizeof(double) : 0);
         for (const DeviceBuf &b : ctx->buf) *workspace_bytes += b.bytes;
+        for (const MaterialHost &m : ctx->materials) *workspace_bytes += m.update_ws.bytes;     // merl_update.hip
     }
     if (device_free || device_total) {
         size_t f = 0, t = 0;

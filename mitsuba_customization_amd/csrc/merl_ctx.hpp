@@ -11,6 +11,8 @@
 //                          tables: mrl_table_grad_batch_mat / mrl_table_grad_queue of merl_hip_fit_table.h): scatter kernels + calls
 //   merl_table_grad_nch.hip  the same adjoint on n-channel tables (mrl_table_grad_batch_nch / mrl_table_grad_queue_nch of
 //                          merl_hip_fit_nch.h): scatter kernels per (cell, channel group of 4) + calls
+//   merl_update.hip        new values for a resident material in place (include/merl_hip_update.h): table images through the upload's
+//                          build kernels, the row marginal on the device (reduction + finishing kernel), GGX parameters
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
 //   merl_ggx_grad_mat.hip  the same with a material id per unit and over queues, onto several GGX materials in one launch
 //                          (mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue of merl_hip_fit_ggx.h): segmented reduction kernels + calls
@@ -52,6 +54,14 @@ namespace mrlabi {
 inline constexpr int kMerlDims[3] = { 90, 90, 180 };
 inline constexpr double kMerlScale[3] = { 1.0 / 1500.0, 1.15 / 1500.0, 1.66 / 1500.0 };
 
+// a device buffer that only grows
+struct DeviceBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    // at least `need` bytes: as it is, or (after the context's stream has drained) freed and allocated anew; contents are not kept
+    int reserve(mrl_ctx *ctx, size_t need);
+};
+
 struct MaterialHost {
     mrl::MaterialDev dev;
     float4 *d_texels = nullptr;
@@ -69,14 +79,9 @@ struct MaterialHost {
     // n-channel tables uploaded as planar arrays: their n_ch channel scales (all ones when the caller passed none), which the
     // n-channel table adjoint needs (merl_table_grad_nch.hip); empty for every other material and for one restored from an image file
     std::vector<double> nch_scale;
-};
-
-// a device buffer that only grows
-struct DeviceBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    // at least `need` bytes: as it is, or (after the context's stream has drained) freed and allocated anew; contents are not kept
-    int reserve(mrl_ctx *ctx, size_t need);
+    // what mrl_material_update_table needs beside the image (merl_update.hip): sized by the material's first update, never moved
+    // afterwards (a captured update points at it), freed with the material; workspace bytes, not material bytes
+    DeviceBuf update_ws;
 };
 
 } // namespace mrlabi

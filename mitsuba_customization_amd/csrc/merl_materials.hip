@@ -435,7 +435,8 @@ int mrl_material_release(mrl_ctx *ctx, int id)
     table_free(ctx, before.d_texels, before.in_arena);
     if (before.d_sampling) (void)hipFree(before.d_sampling);
     if (before.d_sampling2d) (void)hipFree(before.d_sampling2d);
-    m.d_texels = nullptr; m.d_sampling = nullptr; m.d_sampling2d = nullptr;
+    if (before.update_ws.p) (void)hipFree(before.update_ws.p);
+    m.d_texels = nullptr; m.d_sampling = nullptr; m.d_sampling2d = nullptr; m.update_ws = DeviceBuf{};
     ctx->material_bytes -= before.bytes;
     m.bytes = 0;
     return MRL_OK;
@@ -539,6 +540,7 @@ int mrl_material_sampling2d(mrl_ctx *ctx, int id, int *n_ti, int *n_th, double *
     if (!out) return MRL_OK;
     if (max_doubles < need) return fail(ctx, MRL_ERR_INVALID, "buffer too small");
     MRL_HIP(ctx, hipSetDevice(ctx->device));
+    MRL_HIP(ctx, hipStreamSynchronize(ctx->stream));             // an update in place may be rewriting the rows (merl_update.hip)
     MRL_HIP(ctx, hipMemcpy(out, mh.d_sampling2d, need * sizeof(double), hipMemcpyDeviceToHost));
     return MRL_OK;
 }

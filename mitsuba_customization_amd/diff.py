@@ -8,7 +8,17 @@ tables (include/merl_hip_diff_table.h, mrl_table_grad_dir_batch)
 the gradient has flowed through eval into whatever produced wi and wo — a shading-frame rotation, a normal map, a camera pose.  The
 gradient in the material's own parameters is MerlHip.ggx_grad, in a table's texels MerlHip.table_grad (fit.py).  table_eval is the
 same on a table material, and eval serves either kind and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
-tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels]."""
+tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels].
+
+tables= and params= make the same calls differentiable in the MATERIAL as well: the table tensor(s) behind table
+materials, the 7 parameters behind GGX conductors.  Forward writes a tensor's current values into its resident material in place
+(MerlHip.update_table / update_ggx, include/merl_hip_update.h) — only when the tensor has changed since that material last received
+it — and evaluates as before; backward adds the adjoint calls (table_grad*, ggx_grad*) for the tensors that need a gradient:
+
+    T = torch.nn.Parameter(start)                          # f64 [3, n_th, n_td, n_pd] on the device; `mid` was uploaded with these dims
+    loss = ((diff.table_eval(gpu, wi, wo, material=mid, tables=T) - y) ** 2).sum() + smoothness(T)
+    loss.backward()                                        # T.grad = A^T dL/d eval + the regulariser's own gradient"""
+import weakref
 from functools import partial
 
 import torch
@@ -32,12 +42,16 @@ def _any_backward(gpu, wi, wo, grad_rgb, mat=None, material=0, want=("wi", "wo")
 
 
 class _Eval(torch.autograd.Function):
-    """forward_call(wi, wo): an eval of the host; backward_call(wi, wo, grad, want=): the direction gradient of that eval"""
+    """forward_call(wi, wo): an eval of the host; backward_call(wi, wo, grad, want=): the direction gradient of that eval;
+    material_call(wi, wo, grad, needed): the gradients in `values` — the tensors behind the materials (_Materials) — for the
+    positions listed in `needed`, as a list aligned with values (None elsewhere)"""
     @staticmethod
-    def forward(ctx, wi, wo, forward_call, backward_call):
+    def forward(ctx, wi, wo, forward_call, backward_call, material_call=None, *values):
         wi, wo = wi.contiguous(), wo.contiguous()
         ctx.save_for_backward(wi, wo)
         ctx.backward_call = backward_call
+        ctx.material_call = material_call
+        ctx.n_values = len(values)
         return forward_call(wi, wo)
 
     @staticmethod
@@ -45,40 +59,128 @@ class _Eval(torch.autograd.Function):
         wi, wo = ctx.saved_tensors
         # only what the graph asks for: the other output pointer is NULL and that gradient is neither computed nor written
         want = tuple(name for name, needed in zip(("wi", "wo"), ctx.needs_input_grad[:2]) if needed)
+        g = grad_values.contiguous()
         grads = {}
         if want:
-            out = ctx.backward_call(wi, wo, grad_values.contiguous(), want=want)
+            out = ctx.backward_call(wi, wo, g, want=want)
             grads = dict(zip(want, out if len(want) == 2 else (out,)))
-        return grads.get("wi"), grads.get("wo"), None, None
+        needed = [i for i, need in enumerate(ctx.needs_input_grad[5:]) if need]
+        in_values = ctx.material_call(wi, wo, g, needed) if needed else [None] * ctx.n_values
+        return (grads.get("wi"), grads.get("wo"), None, None, None, *in_values)
 
 
-def ggx_eval(ctx, wi, wo, mat=None, material: int = 0):
+class _Materials:
+    """The tensors behind the materials of one differentiable call: entries (kind "table" / "ggx", material id, tensor).
+    refresh() makes every material hold its tensor's current values; gradients() is _Eval's material_call."""
+
+    def __init__(self, gpu, mat, material, tables, params, n_channels=None):
+        self.gpu, self.mat, self.material, self.n_channels = gpu, mat, material, n_channels
+        as_dict = lambda v: {} if v is None else ({int(k): t for k, t in v.items()} if isinstance(v, dict) else {int(material): v})
+        self.entries = [("table", k, t) for k, t in as_dict(tables).items()] + [("ggx", k, t) for k, t in as_dict(params).items()]
+        for kind, _, t in self.entries:
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError("tables= / params=: torch.float64 tensors")
+            if kind == "ggx" and tuple(t.shape) != (7,):
+                raise ValueError("params=: [7] tensors (alpha, eta rgb, k rgb)")
+
+    @property
+    def values(self):
+        return tuple(t for _, _, t in self.entries)
+
+    def refresh(self):
+        # the record lives on the context object: per material the tensor (weakly: an address is reused after a tensor dies), its
+        # address and its version when the material last received it.  MerlHip.update_* and release_material forget a material
+        record = self.gpu.__dict__.setdefault("_resident", {})
+        self.gpu.use_torch_stream()                             # the updates run on the stream the eval behind them will run on
+        for kind, mid, t in self.entries:
+            seen = record.get(mid)
+            if seen is not None and seen[0]() is t and seen[1:] == (t.data_ptr(), t._version):
+                continue
+            if kind == "table":
+                self.gpu.update_table(mid, t.detach(), keep_sampling=True)
+            else:
+                p = t.detach().cpu().tolist()                   # 7 values to the host: waits for whatever computes them
+                self.gpu.update_ggx(mid, p[0], p[1:4], p[4:7])
+            record[mid] = (weakref.ref(t), t.data_ptr(), t._version)
+
+    def gradients(self, wi, wo, g, needed):
+        gpu, out = self.gpu, [None] * len(self.entries)
+        tables = [i for i in needed if self.entries[i][0] == "table"]
+        ggx = [i for i in needed if self.entries[i][0] == "ggx"]
+        if tables:
+            ids = [self.entries[i][1] for i in tables]
+            if self.n_channels is not None:
+                grads = gpu.table_grad_nch(wi, wo, g, self.n_channels, ids, mat=self.mat, material=self.material)
+            elif self.mat is None and ids == [self.material]:
+                grads = (gpu.table_grad(wi, wo, g, material=self.material),)
+            else:                                               # one launch for all targets, split by table_grad_layout
+                grads = gpu.table_grad_mat(wi, wo, g, ids, mat=self.mat, material=self.material)
+            for i, grad in zip(tables, grads):
+                out[i] = grad
+        if ggx:
+            ids = [self.entries[i][1] for i in ggx]
+            if self.mat is None and ids == [self.material]:
+                grads = (gpu.ggx_grad(wi, wo, g, self.material),)
+            else:
+                grads = gpu.ggx_grad_mat(wi, wo, g, ids, mat=self.mat, material=self.material)
+            for i, grad in zip(ggx, grads):
+                out[i] = grad.to(self.entries[i][2].device)
+        return out
+
+
+def _apply(gpu, wi, wo, forward_call, backward_call, mat, material, tables=None, params=None, n_channels=None):
+    if tables is None and params is None:
+        return _Eval.apply(wi, wo, forward_call, backward_call, None)
+    m = _Materials(gpu, mat, material, tables, params, n_channels)
+    m.refresh()
+    return _Eval.apply(wi, wo, forward_call, backward_call, m.gradients, *m.values)
+
+
+def ggx_eval(ctx, wi, wo, mat=None, material: int = 0, params=None):
     """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be GGX conductors:
     the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no live GGX
-    material receives a zero gradient."""
-    return _Eval.apply(wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.ggx_grad_dir, mat=mat, material=material))
+    material receives a zero gradient.
+    params=: an f64 tensor [7] (alpha, eta rgb, k rgb) for the single material, or {id: tensor}: the call is differentiable in them
+    too.  Forward writes a tensor's values into its material with MerlHip.update_ggx when the tensor has changed since — a 7-value
+    read on the host, which waits for whatever computes the tensor; the material holds the values rounded to float, and the
+    gradient is taken there.  Backward is MerlHip.ggx_grad / ggx_grad_mat (sum g . J) for the tensors that need it, at the parameters
+    the material holds THEN: run it before the same material receives other values."""
+    return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.ggx_grad_dir, mat=mat, material=material),
+                  mat, material, params=params)
 
 
-def table_eval(ctx, wi, wo, mat=None, material: int = 0):
+def table_eval(ctx, wi, wo, mat=None, material: int = 0, tables=None):
     """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be RGB tables (MERL /
     customized_measurement): the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose
     id names no live RGB table receives a zero gradient.  The gradient is the one of the trilinear interpolant in the cell eval
-    selects (include/merl_hip_diff_table.h): piecewise smooth, like the function."""
-    return _Eval.apply(wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.table_grad_dir, mat=mat, material=material))
+    selects (include/merl_hip_diff_table.h): piecewise smooth, like the function.
+    tables=: an f64 device tensor [3, n_th, n_td, n_pd] (contiguous) for the single material, or {id: tensor} with mat=: the call is
+    differentiable in the tables too.  Forward writes a tensor into its resident material with MerlHip.update_table(id, T.detach(),
+    keep_sampling=True) — in place, from device memory — only when (T.data_ptr(), T._version) differs from what that material last
+    received, then evaluates.  Backward returns MerlHip.table_grad of the incoming gradient (a dict: one table_grad_mat launch for all
+    tables that need a gradient), beside the direction gradients; each call is issued only if the graph needs it.
+    Under OPT_NEGATIVE = 0 the image is the clamped table, and the gradient returned is the adjoint's: the derivative of the clamped
+    table where a texel is positive — where it is not, the true derivative is 0 (fit.py: A is linear only under OPT_NEGATIVE = 1)."""
+    return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.table_grad_dir, mat=mat, material=material),
+                  mat, material, tables=tables)
 
 
-def eval(ctx, wi, wo, mat=None, material: int = 0):
+def eval(ctx, wi, wo, mat=None, material: int = 0, tables=None, params=None):
     """MerlHip.eval(wi, wo, mat, material), differentiable in wi and wo, for GGX conductors, RGB tables and batches that mix them.
     Single material: the backward pass is the gradient call of that material's kind.  With mat=: the sum of table_grad_dir and
     ggx_grad_dir, each exactly zero on the other's units; units of kinds with no gradient (n-channel, RGL, spectral, released or
-    unknown ids) receive zeros."""
-    return _Eval.apply(wi, wo, partial(ctx.eval, mat=mat, material=material), partial(_any_backward, ctx, mat=mat, material=material))
+    unknown ids) receive zeros.
+    tables= / params=: as in table_eval() and ggx_eval(), for the tables and the conductors of a mixed batch."""
+    return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(_any_backward, ctx, mat=mat, material=material),
+                  mat, material, tables=tables, params=params)
 
 
-def table_eval_nch(ctx, wi, wo, n_channels: int, mat=None, material: int = 0):
+def table_eval_nch(ctx, wi, wo, n_channels: int, mat=None, material: int = 0, tables=None):
     """MerlHip.eval_nch(wi, wo, n_channels, mat, material) of the context `ctx` — [n, n_channels] values —, differentiable in wi and wo.
     The materials must be n-channel tables of exactly n_channels channels: the backward pass of a single material of another kind or
     width raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no such table receives a zero gradient.  One
-    MerlHip.table_grad_dir_nch call for what the graph needs (include/merl_hip_diff_nch.h)."""
-    return _Eval.apply(wi, wo, partial(ctx.eval_nch, n_channels=n_channels, mat=mat, material=material),
-                       partial(ctx.table_grad_dir_nch, n_channels=n_channels, mat=mat, material=material))
+    MerlHip.table_grad_dir_nch call for what the graph needs (include/merl_hip_diff_nch.h).
+    tables=: as in table_eval(), with tensors [n_channels, n_th, n_td, n_pd]; backward is one MerlHip.table_grad_nch launch."""
+    return _apply(ctx, wi, wo, partial(ctx.eval_nch, n_channels=n_channels, mat=mat, material=material),
+                  partial(ctx.table_grad_dir_nch, n_channels=n_channels, mat=mat, material=material), mat, material, tables=tables,
+                  n_channels=n_channels)

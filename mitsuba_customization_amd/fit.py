@@ -8,8 +8,10 @@ A GGX conductor (alpha, eta[3], k[3]): Levenberg-Marquardt on sum w (eval - y)^2
 (fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).  fit_ggx_mat / lm_ggx_mat fit several conductors at once
 from one interleaved set with a material index per unit, on MerlHip.ggx_grad_mat: one eval and one gradient launch per iteration.
 
-The context's lookup / node / cosine options define A.  fit_table uploads iterates that have negative entries, so A is linear
-only with host.OPT_NEGATIVE at keep (1), set before the context's first table is uploaded."""
+The context's lookup / node / cosine options define A.  fit_table makes iterates resident that have negative entries, so A is linear
+only with host.OPT_NEGATIVE at keep (1), set before the context's first table is uploaded.
+An iterate becomes resident in place (MerlHip.update_table / update_ggx): every loop keeps one working material per
+table or conductor and writes each iterate into it — a device tensor from device memory, without visiting the host."""
 from __future__ import annotations
 
 import numpy as np
@@ -32,6 +34,13 @@ def _dot(a, b) -> float:
 def _upload(ctx, table, param, scale) -> int:
     t = table.cpu().numpy() if host._is_tensor(table) else table
     return ctx.upload_table(t, scale) if param is None else ctx.upload_table_param(t, param, scale)
+
+
+def _resident(ctx, mid, table):
+    """the working material `mid` holds `table` (texels only: the fitting loops evaluate, they never sample)"""
+    t = table.contiguous() if host._is_tensor(table) else np.ascontiguousarray(table, np.float64)
+    ctx.update_table(mid, t, keep_sampling=True)
+    return mid
 
 
 def splat(ctx, dims, wi, wo, rgb, param=None, scale=(1.0, 1.0, 1.0)):
@@ -77,13 +86,10 @@ def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
     y = _f64(rgb)
     x, _ = splat(ctx, dims, wi, wo, rgb, param, scale)
     shape_mid = _upload(ctx, np.ones((3,) + tuple(dims)), param, scale)      # what table_grad takes dims, parameterisation and scale from
+    work_mid = _upload(ctx, np.ones((3,) + tuple(dims)), param, scale)       # what every iterate is written into
 
     def A(table):
-        mid = _upload(ctx, table, param, scale)
-        try:
-            return _f64(ctx.eval(wi, wo, material=mid))
-        finally:
-            ctx.release_material(mid)
+        return _f64(ctx.eval(wi, wo, material=_resident(ctx, work_mid, table)))
 
     def At(r):
         return ctx.table_grad(wi, wo, _f32(r), material=shape_mid)
@@ -91,6 +97,7 @@ def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
     try:
         return _cgls(A, At, y, x, iters)
     finally:
+        ctx.release_material(work_mid)
         ctx.release_material(shape_mid)
 
 
@@ -123,13 +130,10 @@ def fit_table_nch(ctx, dims, wi, wo, values, iters, param=None, scale=None):
     y = _f64(values)
     x, _ = splat_nch(ctx, dims, wi, wo, values, param, scale)
     shape_mid = _upload_nch(ctx, np.ones((n_ch,) + tuple(dims)), param, scale)   # what table_grad_nch takes dims, parameterisation and scales from
+    work_mid = _upload_nch(ctx, np.ones((n_ch,) + tuple(dims)), param, scale)    # what every iterate is written into
 
     def A(table):
-        mid = _upload_nch(ctx, table, param, scale)
-        try:
-            return _f64(ctx.eval_nch(wi, wo, n_ch, material=mid))
-        finally:
-            ctx.release_material(mid)
+        return _f64(ctx.eval_nch(wi, wo, n_ch, material=_resident(ctx, work_mid, table)))
 
     def At(r):
         return ctx.table_grad_nch(wi, wo, _f32(r), n_ch, [shape_mid], material=shape_mid)[0]
@@ -137,6 +141,7 @@ def fit_table_nch(ctx, dims, wi, wo, values, iters, param=None, scale=None):
     try:
         return _cgls(A, At, y, x, iters)
     finally:
+        ctx.release_material(work_mid)
         ctx.release_material(shape_mid)
 
 
@@ -201,14 +206,12 @@ def fit_tables(ctx, dims_list, wi, wo, mat, rgb, iters, params=None, scales=None
     weight = [_f64(m)[:, None] for m in member]
     shape_ids = _upload_all(ctx, [np.ones((3,) + tuple(d)) for d in dims_list], params, scales)
     shape_unit = _unit_ids(mat, shape_ids)
+    work_ids = []
 
     def A(tables):
-        ids = _upload_all(ctx, tables, params, scales)
-        try:
-            return _f64(ctx.eval(wi, wo, mat=_unit_ids(mat, ids)))
-        finally:
-            for mid in ids:
-                ctx.release_material(mid)
+        for mid, t in zip(work_ids, tables):
+            _resident(ctx, mid, t)
+        return _f64(ctx.eval(wi, wo, mat=work_unit))
 
     def At(r):
         return ctx.table_grad_mat(wi, wo, _f32(r), shape_ids, mat=shape_unit)
@@ -218,6 +221,8 @@ def fit_tables(ctx, dims_list, wi, wo, mat, rgb, iters, params=None, scales=None
         return [float(rows[m].sum()) for m in member]
 
     try:
+        work_ids += _upload_all(ctx, [np.ones((3,) + tuple(d)) for d in dims_list], params, scales)   # what every iterate is written into
+        work_unit = _unit_ids(mat, work_ids)
         r = y - A(x)
         s = At(r)
         p = list(s)
@@ -239,7 +244,7 @@ def fit_tables(ctx, dims_list, wi, wo, mat, rgb, iters, params=None, scales=None
             for j, rr in enumerate(unit_dots(r)):
                 residuals[j].append(rr ** 0.5 if alpha[j] != 0.0 else residuals[j][-1])
     finally:
-        for mid in shape_ids:
+        for mid in work_ids + shape_ids:
             ctx.release_material(mid)
     return tuple(x), residuals
 
@@ -370,8 +375,8 @@ def lm_ggx_mat(eval_fn, grad_fn, rgb, unit_ids, starts, iters, weights=None):
 
 def fit_ggx_mat(ctx, wi, wo, mat, rgb, starts, iters, weights=None):
     """fit_ggx() for K conductors from one interleaved measurement set: mat[i] (int32) is the index into starts of the material unit
-    i measured; any other value: none.  Every iteration creates the K materials, runs one eval with material ids and one
-    ggx_grad_mat(..., normal=True) on them, and releases them.  Returns K tuples (alpha, eta [3], k [3], residual history) — see
+    i measured; any other value: none.  K working materials are created once; every iteration writes its parameters into them
+    (update_ggx) and runs one eval with material ids and one ggx_grad_mat(..., normal=True) on them.  Returns K tuples (alpha, eta [3], k [3], residual history) — see
     lm_ggx_mat."""
     held = []
     unit = [None]
@@ -381,10 +386,13 @@ def fit_ggx_mat(ctx, wi, wo, mat, rgb, starts, iters, weights=None):
             ctx.release_material(held.pop())
 
     def eval_fn(P):
-        drop()
-        for p in P:
-            held.append(ctx.ggx(float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]]))
-        unit[0] = _unit_ids(mat, held)
+        if not held:
+            for p in P:
+                held.append(ctx.ggx(float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]]))
+            unit[0] = _unit_ids(mat, held)
+        else:
+            for mid, p in zip(held, P):
+                ctx.update_ggx(mid, float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]])
         return ctx.eval(wi, wo, mat=unit[0])
 
     def grad_fn(P, g, h):
@@ -401,7 +409,8 @@ def fit_ggx_mat(ctx, wi, wo, mat, rgb, starts, iters, weights=None):
 
 def fit_ggx(ctx, wi, wo, rgb, start, iters, weights=None):
     """The GGX conductor closest to the measurements: Levenberg-Marquardt on sum w (eval - rgb)^2 from start = (alpha, eta[3], k[3]).
-    Every iteration creates the material, runs eval and ggx_grad(..., normal=True) on it and releases it.  weights: [n] or [n, 3], None = 1.
+    One working material is created once; every iteration writes its parameters into it (update_ggx) and runs eval and
+    ggx_grad(..., normal=True) on it.  weights: [n] or [n, 3], None = 1.
     Returns (alpha, eta [3], k [3], residual history) — see lm_ggx."""
     held = []
 
@@ -410,8 +419,11 @@ def fit_ggx(ctx, wi, wo, rgb, start, iters, weights=None):
             ctx.release_material(held.pop())
 
     def eval_fn(p):
-        drop()
-        held.append(ctx.ggx(float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]]))
+        args = (float(p[0]), [float(x) for x in p[1:4]], [float(x) for x in p[4:7]])
+        if held:
+            ctx.update_ggx(held[0], *args)
+        else:
+            held.append(ctx.ggx(*args))
         return ctx.eval(wi, wo, material=held[0])
 
     def grad_fn(p, g, h):

@@ -82,6 +82,9 @@ FIT_NCH_ABI_SYMBOLS = ("mrl_table_grad_batch_nch", "mrl_table_grad_queue_nch", "
 # every symbol include/merl_hip_fit_ggx.h declares: the GGX parameter gradient with a material id per unit and over wavefront queues
 FIT_GGX_ABI_SYMBOLS = ("mrl_ggx_grad_batch_mat", "mrl_ggx_grad_queue")
 GGX_GRAD_MAX_TARGETS = 16           # MRL_GGX_GRAD_MAX_TARGETS
+# every symbol include/merl_hip_update.h declares: new values for a resident material in place, and the row marginal's read-back
+UPDATE_ABI_SYMBOLS = ("mrl_material_update_table", "mrl_material_update_ggx", "mrl_material_sampling")
+UPDATE_KEEP_SAMPLING = 1            # MRL_UPDATE_KEEP_SAMPLING
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -224,7 +227,7 @@ _FAMILIES = {               # family: (symbol, the parameters between the inputs
 }
 _PDF_FAMILIES = ("batch", "queue", "group")         # the pdf is channel- and wavelength-free: the other families have no pdf mode
 _SCALARS = {"single_id": C.c_int32, "id": C.c_int32, "n": C.c_size_t, "capacity": C.c_size_t, "n_channels": C.c_int, "n_wavelengths": C.c_int,
-            "n_targets": C.c_int}
+            "n_targets": C.c_int, "flags": C.c_int, "alpha": C.c_float, "max_doubles": C.c_size_t}
 # (family, mode): (symbol, middle parameters, inputs, outputs)
 _CALLS = {(family, mode): (symbol.format(mode), middle) + streams
           for family, (symbol, middle) in _FAMILIES.items() for mode, streams in _MODES.items()
@@ -243,6 +246,10 @@ _GGX_TARGETS = ("target_ids", "n_targets", "grad_params", "normal")
 _GGX_GRAD_INS = (_WI, _WO, ("grad_rgb", 3), ("curv_rgb", 3))
 _CALLS["batch", "ggx_grad_mat"] = ("mrl_ggx_grad_batch_mat", _FAMILIES["batch"][1] + _GGX_TARGETS, _GGX_GRAD_INS, ())
 _CALLS["queue", "ggx_grad_mat"] = ("mrl_ggx_grad_queue", _FAMILIES["queue"][1] + _GGX_TARGETS, _GGX_GRAD_INS, ())
+# the calls on one material of include/merl_hip_update.h: no [n, ...] stream at all, the material id and what else the header names
+_CALLS["material", "update_table"] = ("mrl_material_update_table", ("id", "planar", "flags"), (), ())
+_CALLS["material", "update_ggx"] = ("mrl_material_update_ggx", ("id", "alpha", "eta", "k"), (), ())
+_CALLS["material", "sampling"] = ("mrl_material_sampling", ("id", "out", "max_doubles"), (), ())
 
 
 _lib = None
@@ -447,6 +454,32 @@ def _stream_call(owner, family, mode, ins, out=None, width=3, wavelengths=None, 
     args += [_addr(x, np.float32, width if cols == 0 else cols, n, name) for (name, cols), x in zip(out_streams, out)]
     owner._check(getattr(owner._lib, symbol)(*args), symbol)
     return out[0] if len(out_streams) == 1 else out
+
+
+def _material_call(owner, name, **between):
+    """One call of a MerlHip on one material from its row of _CALLS (family "material"): the middle parameters by their names."""
+    symbol, middle, _, _ = _CALLS["material", name]
+    owner._check(getattr(owner._lib, symbol)(owner._ctx, *[between[k] for k in middle]), symbol)
+
+
+def _planar_source(planar, shape):
+    """The address of the planar array an update reads — a C-contiguous numpy float64 array, or a contiguous torch.float64 tensor on
+    the GPU (its device pointer: no copy) — after the checks; shape: (n_channels, n_th, n_td, n_pd).  ValueError otherwise."""
+    shape = tuple(int(d) for d in shape)
+    if _is_tensor(planar):
+        import torch
+        if planar.dtype != torch.float64 or not planar.is_contiguous():
+            raise ValueError("planar: need a contiguous torch.float64 tensor")
+        if not planar.is_cuda:
+            raise ValueError("planar: torch tensors must live on the GPU (pass a numpy array for host data)")
+        got, ptr = tuple(planar.shape), planar.data_ptr()
+    else:
+        if not isinstance(planar, np.ndarray) or planar.dtype != np.float64 or not planar.flags["C_CONTIGUOUS"]:
+            raise ValueError("planar: need a C-contiguous numpy float64 array")
+        got, ptr = planar.shape, planar.ctypes.data
+    if got != shape:
+        raise ValueError(f"planar: shape {tuple(got)}, the material was uploaded from {shape}")
+    return ptr
 
 
 def table_grad_layout(dims_list) -> list:
@@ -714,6 +747,39 @@ class MerlHip:
         self._check(self._lib.mrl_material_load_table_nch(self._ctx, path.encode(), n_channels, sc, C.byref(mid)), "mrl_material_load_table_nch")
         return mid.value
 
+    # ---- new values in place (include/merl_hip_update.h) ----
+    def update_table(self, mid: int, planar, keep_sampling: bool = False):
+        """New values for the resident table or n-channel table `mid` (mrl_material_update_table): same id, same addresses.  planar:
+        f64, contiguous, [n_channels, n_th, n_td, n_pd] as uploaded — a numpy array (staged) or a device tensor (read in place on
+        torch's current stream: no copy, no synchronisation).  keep_sampling: leave both sampling tables as they are.  ValueError
+        for a wrong dtype, layout or shape."""
+        dims = self.material_info(mid)[1]
+        ptr = _planar_source(planar, (self.material_channels(mid),) + tuple(dims))
+        self._prep(planar)
+        self._forget_resident(mid)
+        _material_call(self, "update_table", id=int(mid), planar=ptr, flags=UPDATE_KEEP_SAMPLING if keep_sampling else 0)
+
+    def update_ggx(self, mid: int, alpha: float, eta: Sequence[float], k: Sequence[float]):
+        """New parameters for the GGX material `mid` (mrl_material_update_ggx), validated as ggx() validates them.  Stream-ordered on
+        the stream the context is on — torch's current one after any call with device tensors, else its own; a context that has
+        made no tensor call yet calls use_torch_stream() first if tensor calls are to follow.  Calls with material ids see the new
+        parameters; a graph captured over a single-id call keeps those of its capture (include/merl_hip_update.h)."""
+        self._forget_resident(mid)
+        _material_call(self, "update_ggx", id=int(mid), alpha=alpha, eta=(C.c_float * 3)(*eta), k=(C.c_float * 3)(*k))
+
+    def _forget_resident(self, mid: int):
+        """diff.py records on this object which tensor a material last received (tables= / params=); whoever changes or releases the
+        material drops that record"""
+        self.__dict__.get("_resident", {}).pop(int(mid), None)
+
+    def sampling(self, mid: int):
+        """The row marginal of a table material as the device holds it (mrl_material_sampling): (s [n_th + 1], cdf [n_th + 1],
+        c [n_th]) f64 — the layout of the oracle's sampling_arrays()."""
+        n = int(self.material_info(mid)[1][0])
+        out = np.empty(3 * n + 2, np.float64)
+        _material_call(self, "sampling", id=int(mid), out=out.ctypes.data, max_doubles=out.size)
+        return out[:n + 1].copy(), out[n + 1:2 * n + 2].copy(), out[2 * n + 2:].copy()
+
     def material_channels(self, mid: int) -> int:
         c = C.c_int()
         self._check(self._lib.mrl_material_channels(self._ctx, mid, C.byref(c)), "mrl_material_channels")
@@ -782,6 +848,7 @@ class MerlHip:
 
     def release_material(self, mid: int):
         """Frees the material's device memory; its id becomes a tombstone (batch calls render it as zeros)."""
+        self._forget_resident(mid)
         self._check(self._lib.mrl_material_release(self._ctx, mid), "mrl_material_release")
 
     def memory_info(self) -> dict:
