@@ -39,7 +39,9 @@ extern "C" {
  * unit's position, and grad_wi has the same bits with and without grad_wo.
  * Not offered here: RGB table materials have the same pair of calls in merl_hip_diff_table.h (mrl_table_grad_dir_batch / _queue),
  * n-channel tables in merl_hip_diff_nch.h (mrl_table_grad_dir_batch_nch / _queue_nch).
- * Not offered: RGL materials, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample. */
+ * RGB RGL materials in merl_hip_diff_rgl.h (mrl_rgl_grad_dir_batch / _queue).
+ * Not offered: spectral RGL materials, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and
+ * sample. */
 int mrl_ggx_grad_dir_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                            const int32_t *mat, int32_t single_id, size_t n,
                            float *grad_wi, float *grad_wo);

@@ -55,7 +55,7 @@ extern "C" {
  * DETERMINISM (a contract of these calls): a unit's output bits depend on its own inputs, its material and the context's options
  * alone — the whole-array, material-id, queue and host-array forms return identical bits for the same unit, whatever n, the grid
  * or the unit's position; grad_wi has the same bits with and without grad_wo.
- * Not offered: RGL and spectral RGL tables, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf
+ * Not offered: spectral RGL materials (RGB RGL materials: merl_hip_diff_rgl.h), device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf
  * and sample, the renormalising blend (MRL_OPT_NEGATIVE = 2).  The adjoint in an n-channel table's texels: merl_hip_fit_nch.h. */
 int mrl_table_grad_dir_batch_nch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_values,
                                  const int32_t *mat, int32_t single_id, size_t n, int n_channels,

@@ -55,7 +55,8 @@ extern "C" {
  * or the unit's position; grad_wi has the same bits with and without grad_wo; MRL_OPT_TABLE_LAYOUT rows and bricks return identical
  * bits.
  * Not offered here: n-channel tables have the same pair of calls in merl_hip_diff_nch.h (mrl_table_grad_dir_batch_nch / _queue_nch).
- * Not offered: RGL tables, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample, the
+ * RGB RGL materials have theirs in merl_hip_diff_rgl.h (mrl_rgl_grad_dir_batch / _queue).
+ * Not offered: spectral RGL materials, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample, the
  * renormalising blend (MRL_OPT_NEGATIVE = 2). */
 int mrl_table_grad_dir_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                              const int32_t *mat, int32_t single_id, size_t n,

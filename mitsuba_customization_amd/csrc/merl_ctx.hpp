@@ -21,6 +21,7 @@
 //   merl_ggx_dir_grad.hip  the direction gradient of eval on GGX conductors (mrl_ggx_grad_dir_batch / _queue): streaming kernel + calls
 //   merl_table_dir_grad.hip  the same on RGB tables (mrl_table_grad_dir_batch / _queue)
 //   merl_nch_dir_grad.hip  the same on n-channel tables (mrl_table_grad_dir_batch_nch / _queue_nch)
+//   merl_rgl_dir_grad.hip  the same on RGB RGL materials (mrl_rgl_grad_dir_batch / _queue)
 #pragma once
 #include "../../include/merl_hip.h"
 

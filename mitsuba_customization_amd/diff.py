@@ -1,13 +1,14 @@
 """eval as a differentiable torch operation: forward is MerlHip.eval, backward one MerlHip.ggx_grad_dir call for GGX conductors
 (include/merl_hip_diff.h, mrl_ggx_grad_dir_batch), one MerlHip.table_grad_dir call for MERL / customized_measurement
-tables (include/merl_hip_diff_table.h, mrl_table_grad_dir_batch), both for a batch with material ids.  After
+tables (include/merl_hip_diff_table.h, mrl_table_grad_dir_batch), one MerlHip.rgl_grad_dir call for RGB RGL materials
+(include/merl_hip_diff_rgl.h, mrl_rgl_grad_dir_batch), their sum for a batch with material ids.  After
 
     rgb = diff.ggx_eval(gpu, wi, wo, material=mid)        # wi, wo: [n, 3] float32 device tensors, possibly results of torch code
     loss(rgb).backward()
 
 the gradient has flowed through eval into whatever produced wi and wo — a shading-frame rotation, a normal map, a camera pose.  The
 gradient in the material's own parameters is MerlHip.ggx_grad, in a table's texels MerlHip.table_grad (fit.py).  table_eval is the
-same on a table material, and eval serves either kind and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
+same on a table material, rgl_eval on an RGL material, and eval serves every one of these kinds and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
 tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels].
 
 tables= and params= make the same calls differentiable in the MATERIAL as well: the table tensor(s) behind table
@@ -28,17 +29,33 @@ from . import host
 
 def _any_backward(gpu, wi, wo, grad_rgb, mat=None, material=0, want=("wi", "wo")):
     """Single material: the gradient call of its kind (a kind without one: mrl_table_grad_dir_batch's MRL_ERR_MATERIAL).  With ids: the
-    sum of the two calls — each writes exact zeros on the other's units and on units of kinds without a gradient, so the sum is exact."""
+    sum of the table and the GGX call — each writes exact zeros on the other's units and on units of kinds without a gradient, so the
+    sum is exact — and, only when the context holds a live RGB RGL material, of the RGL call as a third: a context without one makes
+    exactly the two calls it made before RGL materials had a gradient."""
     if mat is None:
         try:
             kind = gpu.material_info(material)[0]
         except host.MerlHipError:
             kind = None
-        call = gpu.ggx_grad_dir if kind == host.KIND_GGX else gpu.table_grad_dir
+        call = gpu.ggx_grad_dir if kind == host.KIND_GGX else gpu.rgl_grad_dir if kind == host.KIND_RGL else gpu.table_grad_dir
         return call(wi, wo, grad_rgb, material=material, want=want)
     table = gpu.table_grad_dir(wi, wo, grad_rgb, mat=mat, want=want)
     ggx = gpu.ggx_grad_dir(wi, wo, grad_rgb, mat=mat, want=want)
-    return table + ggx if len(want) == 1 else tuple(t + g for t, g in zip(table, ggx))
+    parts = [table, ggx] + ([gpu.rgl_grad_dir(wi, wo, grad_rgb, mat=mat, want=want)] if _holds_rgl(gpu) else [])
+    if len(want) == 1:
+        return sum(parts[1:], parts[0])
+    return tuple(sum(side[1:], side[0]) for side in zip(*parts))
+
+
+def _holds_rgl(gpu):
+    """does the context hold a live RGB RGL material?  (a released slot has no info: MerlHipError)"""
+    for mid in range(gpu.material_count()):
+        try:
+            if gpu.material_info(mid)[0] == host.KIND_RGL:
+                return True
+        except host.MerlHipError:
+            pass
+    return False
 
 
 class _Eval(torch.autograd.Function):
@@ -165,11 +182,20 @@ def table_eval(ctx, wi, wo, mat=None, material: int = 0, tables=None):
                   mat, material, tables=tables)
 
 
+def rgl_eval(ctx, wi, wo, mat=None, material: int = 0):
+    """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be RGB RGL materials
+    (upload_rgl / load_rgl): the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose
+    id names no live RGB RGL material receives a zero gradient.  The gradient is the exact one of the piecewise function in the cells
+    eval selects (include/merl_hip_diff_rgl.h): piecewise smooth, like the function.  The file's values are not differentiable."""
+    return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.rgl_grad_dir, mat=mat, material=material),
+                  mat, material)
+
+
 def eval(ctx, wi, wo, mat=None, material: int = 0, tables=None, params=None):
-    """MerlHip.eval(wi, wo, mat, material), differentiable in wi and wo, for GGX conductors, RGB tables and batches that mix them.
-    Single material: the backward pass is the gradient call of that material's kind.  With mat=: the sum of table_grad_dir and
-    ggx_grad_dir, each exactly zero on the other's units; units of kinds with no gradient (n-channel, RGL, spectral, released or
-    unknown ids) receive zeros.
+    """MerlHip.eval(wi, wo, mat, material), differentiable in wi and wo, for GGX conductors, RGB tables, RGB RGL materials and batches
+    that mix them.  Single material: the backward pass is the gradient call of that material's kind.  With mat=: the sum of
+    table_grad_dir and ggx_grad_dir — and of rgl_grad_dir when the context holds a live RGB RGL material —, each exactly zero on the
+    others' units; units of kinds with no gradient (n-channel, spectral RGL, released or unknown ids) receive zeros.
     tables= / params=: as in table_eval() and ggx_eval(), for the tables and the conductors of a mixed batch."""
     return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(_any_backward, ctx, mat=mat, material=material),
                   mat, material, tables=tables, params=params)

@@ -74,6 +74,8 @@ DIFF_ABI_SYMBOLS = ("mrl_ggx_grad_dir_batch", "mrl_ggx_grad_dir_queue")
 DIFF_TABLE_ABI_SYMBOLS = ("mrl_table_grad_dir_batch", "mrl_table_grad_dir_queue")
 # every symbol include/merl_hip_diff_nch.h declares: the same gradient on n-channel table materials
 DIFF_NCH_ABI_SYMBOLS = ("mrl_table_grad_dir_batch_nch", "mrl_table_grad_dir_queue_nch")
+# every symbol include/merl_hip_diff_rgl.h declares: the same gradient on RGB RGL materials
+DIFF_RGL_ABI_SYMBOLS = ("mrl_rgl_grad_dir_batch", "mrl_rgl_grad_dir_queue")
 # every symbol include/merl_hip_fit_table.h declares: the table adjoint with a material id per unit and over wavefront queues
 FIT_TABLE_ABI_SYMBOLS = ("mrl_table_grad_batch_mat", "mrl_table_grad_queue", "mrl_table_grad_layout")
 TABLE_GRAD_MAX_TARGETS = 16         # MRL_TABLE_GRAD_MAX_TARGETS
@@ -309,6 +311,8 @@ def load_library(path: Optional[str] = None):
     L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
     L.mrl_table_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_table_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
+    L.mrl_rgl_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
+    L.mrl_rgl_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
     L.mrl_table_grad_dir_batch_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp, fp]
     L.mrl_table_grad_dir_queue_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp, fp]
     L.mrl_generate_pairs.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, fp, fp, fp]
@@ -1065,6 +1069,12 @@ class MerlHip:
         channels, gets zeros.  Same conventions as ggx_grad_dir()."""
         return self._grad_dir_call("mrl_table_grad_dir_batch_nch", wi, wo, grad_values, mat, material, want, out, n_channels)
 
+    def rgl_grad_dir(self, wi, wo, grad_rgb, mat=None, material: int = 0, want=("wi", "wo"), out=None):
+        """The direction gradient of eval on RGB RGL materials (mrl_rgl_grad_dir_batch, include/merl_hip_diff_rgl.h): per unit
+        grad_wi = sum_c grad_rgb_c d eval_c / d wi and the same in wo, [n, 3] f32, overwritten; a dead unit, and with mat= a unit whose
+        id names no live RGB RGL material, gets zeros.  Same conventions as ggx_grad_dir()."""
+        return self._grad_dir_call("mrl_rgl_grad_dir_batch", wi, wo, grad_rgb, mat, material, want, out)
+
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
 
@@ -1141,6 +1151,11 @@ class MerlHip:
         """table_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_dir_queue); other slots of `out` stay as
         they are (outputs allocated here start from zeros)."""
         return self._grad_dir_call("mrl_table_grad_dir_queue", wi, wo, grad_rgb, mat, material, want, out, queue=(queue, count, capacity))
+
+    def rgl_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
+        """rgl_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_rgl_grad_dir_queue); other slots of `out` stay as they
+        are (outputs allocated here start from zeros)."""
+        return self._grad_dir_call("mrl_rgl_grad_dir_queue", wi, wo, grad_rgb, mat, material, want, out, queue=(queue, count, capacity))
 
     def table_grad_dir_queue_nch(self, wi, wo, grad_values, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None,
                                  want=("wi", "wo"), out=None):

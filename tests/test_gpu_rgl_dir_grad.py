@@ -1,0 +1,320 @@
+"""mrl_rgl_grad_dir_batch / mrl_rgl_grad_dir_queue on the device against the autograd reference of tests/rgl_dir_grad_reference.py
+(which tests/test_rgl_dir_grad_cpu.py ties to the oracle's eval): the files and units of the CPU test — 4,096 random pairs of length
+0.5 .. 2 and the fixed block (grazing, near-mirror, wi at an elevation node and below the first, dead units whose g is NaN / inf) per
+file — at the project's bar, |G - R|_2 <= 1e-6 S per unit and side, S = sum_c |g_c| |J_c|_2, on every live unit the reference does
+not excuse; exact +0.0 on dead units; everything finite.  Then the shapes around a wave and a block, and bit-identity between device
+and host arrays, one output and both, material ids and a single material (the kernels compiled for a bracket shape against the one
+that tests it at run time), the queue form (also replayed from a captured graph); the error codes; the autograd wrappers
+diff.rgl_eval and diff.eval(mat=ids) through a rotation of the shading frame; and a batch without RGL ids, bit for bit what the table
+and GGX calls summed by hand return.
+
+Measured on MI355X, worst |G - R| / S per file, wi / wo side, in units of 1e-8: iso 5.81 / 5.72, iso_nojac 5.27 / 5.66,
+iso_theta1 5.53 / 5.43, iso_phi2 5.43 / 5.51, aniso 5.33 / 5.26, aniso_red2 4.90 / 5.34, aniso_red4 5.10 / 5.51, aniso_uneven
+5.49 / 5.05, iso_rows 5.49 / 5.80, iso_cols 5.52 / 5.67, iso_negative 5.72 / 5.52, ggx_res32 5.66 / 5.92 — the rounding of the f32
+output (2^-24 sqrt(3) = 1.03e-7 at most); 3 to 5 fixed units excused per file, no random one; the file runs in 3 s."""
+import numpy as np
+import pytest
+
+from tests import rgl_dir_grad_reference as rref
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -777.25
+WORST = {"device": 0.0}
+
+
+def to_dev(*arrs):
+    import torch
+    return [torch.from_numpy(np.array(a)).cuda() for a in arrs]            # a copy: the cases are read-only
+
+
+def bits(x):
+    x = x.cpu().numpy() if hasattr(x, "cpu") else x
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def same_bits(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def sentinel(n, device=True):
+    a = np.full((n, 3), SENTINEL, np.float32)
+    return to_dev(a)[0] if device else a
+
+
+def check(Gi, Go, d, sel, tag):
+    Gi, Go = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in (Gi, Go))
+    wi = rref.check_side(Gi, d["Ji"][sel], d["g"][sel], d["alive"][sel], d["excused"][sel], tag + " wi")
+    wo = rref.check_side(Go, d["Jo"][sel], d["g"][sel], d["alive"][sel], d["excused"][sel], tag + " wo")
+    print(f"{tag}: worst |G - R| / S = {wi:.2e} (wi) {wo:.2e} (wo); {int(d['excused'][sel].sum())} units excused")
+    return max(wi, wo)
+
+
+def shape_selection(d, n):
+    """the first units of the random block and the last of the fixed one (dead units with NaN / inf in g among them)"""
+    sel = np.r_[0:(n + 1) // 2, len(d["wi"]) - n // 2:len(d["wi"])]
+    assert len(sel) == n
+    return sel
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    """one context with an isotropic and an anisotropic RGL file, a MERL-shaped table, a GGX conductor and a spectral RGL file"""
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need the MI355X box"
+    from mitsuba_customization_amd import host, synth
+    ctx = host.MerlHip(0)
+    data = [rref.case_data("iso"), rref.case_data("aniso")]
+    rgl = [ctx.upload_rgl(d["fields"]) for d in data]
+    table = ctx.upload_table_param(synth.ggx_tab_table(3, (7, 5, 12)), 0, (0.5, 1.0, 2.0))
+    ggx = ctx.ggx(0.3, (0.143, 0.375, 1.442), (3.983, 2.386, 1.603))
+    spectral = ctx.upload_rgl(synth.make_rgl_fields(seed=61, n_phi=1, n_theta=4, res=8, n_wavelengths=4))
+    yield dict(ctx=ctx, host=host, data=data, rgl=rgl, table=table, ggx=ggx, spectral=spectral)
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", rref.FILE_NAMES)
+def test_parity_with_autograd(name):
+    from mitsuba_customization_amd import host
+    d = rref.case_data(name)
+    with host.MerlHip(0) as ctx:
+        mid = ctx.upload_rgl(d["fields"])
+        Gi, Go = (x.cpu().numpy() for x in ctx.rgl_grad_dir(*to_dev(d["wi"], d["wo"], d["g"]), material=mid))
+        ids = to_dev(np.full(len(d["wi"]), mid, np.int32))[0]
+        Mi, Mo = ctx.rgl_grad_dir(*to_dev(d["wi"], d["wo"], d["g"]), mat=ids)
+    WORST["device"] = max(WORST["device"], check(Gi, Go, d, slice(None), name))
+    print(f"worst so far: {WORST['device']:.2e}")
+    assert same_bits(Mi, Gi) and same_bits(Mo, Go)                   # compiled for the bracket shape == tested at run time
+    held = d["alive"] & ~d["excused"]
+    assert np.abs(Gi[held]).max() > 0 and np.abs(Go[held]).max() > 0
+    assert (~d["alive"]).sum() == rref.N_DEAD_FIXED and not np.isfinite(d["g"][~d["alive"]]).any()
+
+
+@pytest.mark.parametrize("n", (1, 63, 64, 65, 257, 4096))
+def test_shapes_around_a_wave_and_a_block(gpu, n):
+    for d, mid in zip(gpu["data"], gpu["rgl"]):
+        sel = shape_selection(d, n)
+        Gi, Go = gpu["ctx"].rgl_grad_dir(*to_dev(d["wi"][sel], d["wo"][sel], d["g"][sel]), material=mid)
+        check(Gi, Go, d, sel, f"{d['name']} n={n}")
+        whole = gpu["ctx"].rgl_grad_dir(*to_dev(d["wi"], d["wo"], d["g"]), material=mid)
+        assert same_bits(Gi, whole[0].cpu().numpy()[sel]) and same_bits(Go, whole[1].cpu().numpy()[sel])
+
+
+def test_one_output_and_host_arrays(gpu):
+    ctx, host = gpu["ctx"], gpu["host"]
+    for d, mid in zip(gpu["data"], gpu["rgl"]):
+        n = len(d["wi"])
+        wi, wo, g = to_dev(d["wi"], d["wo"], d["g"])
+        Gi, Go = ctx.rgl_grad_dir(wi, wo, g, material=mid)
+        assert same_bits(ctx.rgl_grad_dir(wi, wo, g, material=mid, want="wi"), Gi)
+        assert same_bits(ctx.rgl_grad_dir(wi, wo, g, material=mid, want="wo"), Go)
+        # a NULL output is not written
+        outs = [sentinel(n), sentinel(n)]
+        ctx.use_torch_stream()
+        assert ctx._lib.mrl_rgl_grad_dir_batch(ctx._ctx, wi.data_ptr(), wo.data_ptr(), g.data_ptr(), None, mid, n, outs[0].data_ptr(), None) == 0
+        ctx.synchronize()
+        assert same_bits(outs[0], Gi) and same_bits(outs[1], sentinel(n, device=False))
+        chunk = ctx.get_option(host.OPT_HOST_CHUNK)
+        ctx.set_option(host.OPT_HOST_CHUNK, 1024)
+        try:
+            arrs = [np.ascontiguousarray(d[k]) for k in ("wi", "wo", "g")]
+            Hi, Ho = ctx.rgl_grad_dir(*arrs, material=mid)
+            mat = np.full(n, mid, np.int32)
+            Ii, Io = ctx.rgl_grad_dir(*arrs, mat=mat)
+        finally:
+            ctx.set_option(host.OPT_HOST_CHUNK, chunk)
+        assert isinstance(Hi, np.ndarray) and same_bits(Hi, Gi) and same_bits(Ho, Go) and same_bits(Ii, Gi) and same_bits(Io, Go)
+
+
+def mixed_ids(gpu, n, seed):
+    choices = np.array(gpu["rgl"] + [gpu["table"], gpu["ggx"], gpu["spectral"]], np.int32)
+    return choices[np.random.default_rng(seed).integers(0, len(choices), n)]
+
+
+def test_material_ids(gpu):
+    import torch
+    ctx, d = gpu["ctx"], gpu["data"][0]
+    n = 4099
+    sel = shape_selection(d, n)
+    wi, wo, g = to_dev(d["wi"][sel], d["wo"][sel], d["g"][sel])
+    mat = mixed_ids(gpu, n, 7)
+    mat[::41] = -1; mat[5::43] = ctx.material_count() + 3
+    Gi, Go = ctx.rgl_grad_dir(wi, wo, g, mat=to_dev(mat)[0])
+    assert same_bits(ctx.rgl_grad_dir(wi, wo, g, mat=to_dev(mat)[0], want="wo"), Go)
+    for mid in gpu["rgl"]:
+        Si, So = ctx.rgl_grad_dir(wi, wo, g, material=mid)
+        mine = mat == mid
+        assert mine.sum() > 100
+        assert same_bits(Gi.cpu().numpy()[mine], Si.cpu().numpy()[mine]) and same_bits(Go.cpu().numpy()[mine], So.cpu().numpy()[mine])
+        assert float(Si.abs().max()) > 0
+    other = ~np.isin(mat, gpu["rgl"])
+    assert other.sum() > 100
+    zeros = np.zeros((int(other.sum()), 3), np.float32)
+    assert same_bits(Gi.cpu().numpy()[other], zeros) and same_bits(Go.cpu().numpy()[other], zeros)
+    assert torch.isfinite(Gi).all() and torch.isfinite(Go).all()
+
+
+@pytest.mark.parametrize("with_ids", (False, True), ids=("single", "ids"))
+def test_queue(gpu, with_ids):
+    import torch
+    ctx, d = gpu["ctx"], gpu["data"][1]
+    cap = 1000
+    sel = shape_selection(d, cap)
+    wi, wo, g = to_dev(d["wi"][sel], d["wo"][sel], d["g"][sel])
+    kw = dict(mat=to_dev(mixed_ids(gpu, cap, 8))[0]) if with_ids else dict(material=gpu["rgl"][1])
+    Wi, Wo = (x.cpu().numpy() for x in ctx.rgl_grad_dir(wi, wo, g, **kw))
+    order = np.random.default_rng(9).permutation(cap).astype(np.int32)
+    queue = to_dev(order)[0]
+    blank = sentinel(cap, device=False)
+
+    def expect(whole, count):
+        e = blank.copy()
+        e[order[:count]] = whole[order[:count]]
+        return e
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for c in (300, 5000):
+        count.fill_(c)
+        outs = (sentinel(cap), sentinel(cap))
+        ctx.rgl_grad_dir_queue(wi, wo, g, queue, count, out=outs, **kw)
+        ctx.synchronize()
+        served = min(c, cap)
+        assert same_bits(outs[0], expect(Wi, served)) and same_bits(outs[1], expect(Wo, served)), c
+    # one capture (a single branch: one launch on one stream), replayed once with another device-side count
+    outs = (sentinel(cap), sentinel(cap))
+    count.fill_(3)
+    torch.cuda.synchronize()
+    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    with torch.cuda.graph(graph, stream=side):
+        ctx.rgl_grad_dir_queue(wi, wo, g, queue, count, out=outs, **kw)
+    for o in outs:
+        o.fill_(SENTINEL)
+    count.fill_(300)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert same_bits(outs[0], expect(Wi, 300)) and same_bits(outs[1], expect(Wo, 300))
+    ctx.use_own_stream()
+
+
+def test_error_codes(gpu):
+    import torch
+    ctx, host, d = gpu["ctx"], gpu["host"], gpu["data"][0]
+    n = 64
+    wi, wo, g = to_dev(d["wi"][:n], d["wo"][:n], d["g"][:n])
+    queue = torch.arange(n, dtype=torch.int32, device="cuda")
+    count = torch.full((1,), n, dtype=torch.int32, device="cuda")
+    for mid in (gpu["table"], gpu["ggx"], gpu["spectral"], ctx.material_count() + 5, -1):
+        with pytest.raises(host.MerlHipError) as e:
+            ctx.rgl_grad_dir(wi, wo, g, material=mid)
+        assert e.value.status == host.ERR_MATERIAL, mid
+        with pytest.raises(host.MerlHipError) as e:
+            ctx.rgl_grad_dir_queue(wi, wo, g, queue, count, material=mid)
+        assert e.value.status == host.ERR_MATERIAL, mid
+    mid = gpu["rgl"][0]
+    Gi, Go = sentinel(n), sentinel(n)
+    batch, queued = ctx._lib.mrl_rgl_grad_dir_batch, ctx._lib.mrl_rgl_grad_dir_queue
+    p = [wi.data_ptr(), wo.data_ptr(), g.data_ptr()]
+    ctx.use_torch_stream()
+    for missing in range(3):
+        ins = [None if i == missing else x for i, x in enumerate(p)]
+        assert batch(ctx._ctx, *ins, None, mid, n, Gi.data_ptr(), Go.data_ptr()) == host.ERR_INVALID
+        assert queued(ctx._ctx, *ins, None, mid, queue.data_ptr(), count.data_ptr(), n, Gi.data_ptr(), Go.data_ptr()) == host.ERR_INVALID
+    assert batch(ctx._ctx, *p, None, mid, n, None, None) == host.ERR_INVALID
+    assert queued(ctx._ctx, *p, None, mid, None, count.data_ptr(), n, Gi.data_ptr(), Go.data_ptr()) == host.ERR_INVALID
+    assert queued(ctx._ctx, d["wi"][:n].ctypes.data, *p[1:], None, mid, queue.data_ptr(), count.data_ptr(), n, Gi.data_ptr(),
+                  Go.data_ptr()) == host.ERR_POINTER_MIX
+    with pytest.raises(host.MerlHipError) as e:
+        ctx.rgl_grad_dir(wi, d["wo"][:n], d["g"][:n], material=mid)
+    assert e.value.status == host.ERR_POINTER_MIX
+    # n == 0 / capacity == 0: MRL_OK, nothing touched
+    assert batch(ctx._ctx, *p, None, mid, 0, Gi.data_ptr(), Go.data_ptr()) == 0
+    assert queued(ctx._ctx, *p, None, mid, queue.data_ptr(), count.data_ptr(), 0, Gi.data_ptr(), Go.data_ptr()) == 0
+    ctx.synchronize()
+    assert same_bits(Gi, sentinel(n, device=False)) and same_bits(Go, sentinel(n, device=False))
+
+
+def _rotation(angles):
+    """the shading frame turned by (ax, ay) about x and y (torch f64, differentiable)"""
+    import torch
+    ax, ay = angles[0], angles[1]
+    one, zero = torch.ones_like(ax), torch.zeros_like(ax)
+    rx = torch.stack([torch.stack([one, zero, zero]), torch.stack([zero, torch.cos(ax), -torch.sin(ax)]), torch.stack([zero, torch.sin(ax), torch.cos(ax)])])
+    ry = torch.stack([torch.stack([torch.cos(ay), zero, torch.sin(ay)]), torch.stack([zero, one, zero]), torch.stack([-torch.sin(ay), zero, torch.cos(ay)])])
+    return rx @ ry
+
+
+def test_autograd_through_a_rotation_of_the_shading_frame(gpu):
+    """d loss / d angles through diff.rgl_eval (one material) and diff.eval(mat=ids): the wrappers' chain equals the reference's —
+    the reference Jacobians of the ROTATED Float directions contracted with the same weights and pushed through the same rotation
+    by torch.  Per unit the two gradients agree to 1e-6 S, so the sums agree to 1e-6 sum_u S_u |d dir / d angle|."""
+    import torch
+    from mitsuba_customization_amd import diff
+    ctx = gpu["ctx"]
+    d = gpu["data"][0]
+    sel = np.flatnonzero(d["alive"])[:2000]
+    angles0 = torch.tensor([0.05, -0.03], dtype=torch.float64)
+    w = to_dev(d["g"][sel])[0]
+    wi_w, wo_w = (torch.from_numpy(np.array(d[k][sel], np.float64)) for k in ("wi", "wo"))
+
+    def local(angles, dev):
+        r = _rotation(angles)
+        return (wi_w.to(dev) @ r.to(dev).T).to(torch.float32), (wo_w.to(dev) @ r.to(dev).T).to(torch.float32)
+    for kind in ("single", "ids"):
+        mat = to_dev(np.where(np.arange(len(sel)) % 3 == 0, gpu["table"], gpu["rgl"][0]).astype(np.int32))[0] if kind == "ids" else None
+        angles = angles0.clone().requires_grad_(True)
+        a, b = local(angles, "cuda")
+        rgb = (diff.rgl_eval(ctx, a, b, material=gpu["rgl"][0]) if kind == "single" else diff.eval(ctx, a, b, mat=mat))
+        assert same_bits(rgb.detach(), ctx.eval(a.detach(), b.detach(), mat=mat, material=gpu["rgl"][0]))
+        (rgb * w).sum().backward()
+        got = angles.grad.numpy()
+        # the reference's chain at the same Float directions
+        a32, b32 = a.detach().cpu().numpy(), b.detach().cpu().numpy()
+        Ji, Jo, _, alive, exc = rref.jacobian(d["arrays"], a32, b32)
+        is_rgl = np.ones(len(sel), bool) if mat is None else (mat.cpu().numpy() == gpu["rgl"][0])
+        held = alive & ~exc & is_rgl
+        Ri, Si = rref.contract(Ji, d["g"][sel], held)
+        Ro, So = rref.contract(Jo, d["g"][sel], held)
+        if mat is not None:                                       # the table units' share, from the table call
+            Ti, To = ctx.table_grad_dir(a.detach(), b.detach(), w, mat=mat)
+            Ri, Ro = Ri + Ti.cpu().numpy().astype(np.float64), Ro + To.cpu().numpy().astype(np.float64)
+        # units the reference excuses: take the device's own gradient on both sides (nothing is asked of them)
+        Gi, Go = (x.cpu().numpy().astype(np.float64) for x in ctx.rgl_grad_dir(a.detach(), b.detach(), w, mat=mat, material=gpu["rgl"][0]))
+        skip = is_rgl & ~held
+        Ri[skip], Ro[skip] = Gi[skip], Go[skip]
+        ang = angles0.clone().requires_grad_(True)
+        a64, b64 = wi_w @ _rotation(ang).T, wo_w @ _rotation(ang).T
+        ((a64 * torch.from_numpy(Ri)).sum() + (b64 * torch.from_numpy(Ro)).sum()).backward()
+        want = ang.grad.numpy()
+        lever = float((Si * np.sqrt((d["wi"][sel].astype(np.float64) ** 2).sum(-1)) + So * np.sqrt((d["wo"][sel].astype(np.float64) ** 2).sum(-1))).sum())
+        print(f"{kind}: d loss / d angles {got} against {want}; tolerance {1e-6 * lever:.2e}")
+        assert np.abs(got - want).max() <= 1e-6 * lever + 1e-12 * np.abs(want).max() and np.abs(want).max() > 0
+        assert held.sum() > 0.6 * is_rgl.sum()
+
+
+def test_a_batch_without_rgl_ids_returns_the_bits_of_the_two_calls(gpu):
+    """The context holds RGL materials, the batch names none: diff.eval's backward adds the RGL call's exact zeros to the table and GGX
+    calls summed by hand — the same bits."""
+    import torch
+    from mitsuba_customization_amd import diff
+    ctx, d = gpu["ctx"], gpu["data"][0]
+    live = d["alive"]
+    wi0, wo0, w = to_dev(d["wi"][live], d["wo"][live], d["g"][live])
+    choices = np.array([gpu["table"], gpu["ggx"], gpu["spectral"], -1], np.int32)
+    mat = to_dev(choices[np.random.default_rng(11).integers(0, len(choices), len(wi0))])[0]
+    Ti, To = ctx.table_grad_dir(wi0, wo0, w, mat=mat)
+    Xi, Xo = ctx.ggx_grad_dir(wi0, wo0, w, mat=mat)
+    Ri, Ro = ctx.rgl_grad_dir(wi0, wo0, w, mat=mat)
+    assert not bits(Ri).any() and not bits(Ro).any()
+    wi, wo = wi0.clone().requires_grad_(True), wo0.clone().requires_grad_(True)
+    (diff.eval(ctx, wi, wo, mat=mat) * w).sum().backward()
+    assert same_bits(wi.grad, Ti + Xi) and same_bits(wo.grad, To + Xo)
+    assert float(Ti.abs().max()) > 0 and float(Xi.abs().max()) > 0
+    # and with RGL ids among them the third call is what serves them
+    mat2 = to_dev(mixed_ids(gpu, len(wi0), 12))[0]
+    Ri, Ro = ctx.rgl_grad_dir(wi0, wo0, w, mat=mat2)
+    Ti, To = ctx.table_grad_dir(wi0, wo0, w, mat=mat2)
+    Xi, Xo = ctx.ggx_grad_dir(wi0, wo0, w, mat=mat2)
+    wi, wo = wi0.clone().requires_grad_(True), wo0.clone().requires_grad_(True)
+    (diff.eval(ctx, wi, wo, mat=mat2) * w).sum().backward()
+    assert same_bits(wi.grad, Ti + Xi + Ri) and same_bits(wo.grad, To + Xo + Ro)
+    rgl_units = np.isin(mat2.cpu().numpy(), gpu["rgl"])
+    assert float(Ri[torch.from_numpy(rgl_units).cuda()].abs().max()) > 0 and not Ri.cpu().numpy()[~rgl_units].any()

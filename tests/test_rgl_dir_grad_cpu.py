@@ -1,0 +1,198 @@
+"""The direction gradient of eval on RGB RGL materials (mrl_rgl_grad_dir_batch / _queue, include/merl_hip_diff_rgl.h) without a GPU:
+the autograd reference of tests/rgl_dir_grad_reference.py is shown to differentiate eval's own function (its f64 value against the
+oracle's rgl_eval_pdf_batch and the host-compiled product's eval), the per-lane function the kernel runs
+(csrc/merl_rgl_dir_grad.hpp, rgl::eval_dir_grad) is compiled for the host and held to the project's bar on every file of
+rgl_dir_grad_reference.FILES, the identities of the header are checked, the header and the library carry the calls, and the
+single-material kernels compile for gfx950 without scratch.
+
+Measured here (host build: the reciprocal and square-root seeds are the host's), 4,096 random units + the fixed block per file, 12
+files, both sides: worst |G - R| / S = 5.92e-8, the rounding of the f32 output (2^-24 sqrt(3) = 1.03e-7 at most); 0 random units
+excused on every file, 3 to 5 of the 20 live fixed ones; the reference's value agrees with the oracle's Float result to 4.9e-8 of the
+batch's largest value (the Float rounding of the result)."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import rgl_dir_grad_reference as rref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+WORST = {"harness": 0.0}
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc missing")
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def _close(got, want, top):
+    """1e-6 relative: of the value, or of a tenth of the batch's largest (the host tolerance of tests/test_rgl_cpu.py)"""
+    want = np.asarray(want, np.float64)
+    return float((np.abs(np.asarray(got, np.float64) - want) / (np.abs(want) + 0.1 * top)).max())
+
+
+# ------------------------------------------------------------------ the reference
+@pytest.mark.parametrize("name", rref.FILE_NAMES)
+def test_reference_stays_within_the_cap_and_restates_the_oracle(name):
+    """case_data asserts the cap on excused units (1 % of the live random units) on the reference alone; the function the
+    reference differentiates is the oracle's eval: its f64 value against rgl_eval_pdf_batch's Float to 1e-6 relative."""
+    d = rref.case_data(name)
+    held = d["alive"] & ~d["excused"]
+    rgb, _ = d["oracle"].eval_pdf(d["wi"], d["wo"])
+    assert held[:d["n_random"]].sum() >= 0.99 * d["alive"][:d["n_random"]].sum()
+    top = float(np.abs(rgb).max())
+    err = _close(d["val"][held], rgb[held], top)
+    print(f"{name}: {int(d['excused'][:d['n_random']].sum())} random and {int(d['excused'][d['n_random']:].sum())} fixed units excused; "
+          f"value against the oracle {err:.1e}")
+    assert err <= 1e-6 and top > 0
+    assert not rgb[~d["alive"]].any()
+    if name == "iso_negative":
+        assert (d["val"][held] == 0).any(axis=-1).mean() > 0.02            # the channel clamp is active on part of the units
+
+
+# ------------------------------------------------------------------ the product's per-lane function on the host
+@needs_hipcc
+@pytest.mark.parametrize("name", rref.FILE_NAMES)
+def test_per_lane_function_on_the_host_meets_the_bar(name, tmp_path_factory):
+    d = rref.case_data(name)
+    Gi, Go, ev = rref.run_harness(rref.build_harness(tmp_path_factory), tmp_path_factory.mktemp("rgl_dir_grad"), d["fields"], d["wi"], d["wo"], d["g"])
+    held = d["alive"] & ~d["excused"]
+    # (a) the harness's eval — the product's image and per-unit function — is the function the reference differentiates
+    rgb, _ = d["oracle"].eval_pdf(d["wi"], d["wo"])
+    top = float(np.abs(rgb).max())
+    assert _close(ev[held], d["val"][held], top) <= 1e-6 and _close(ev[held], rgb[held], top) <= 1e-6
+    # (b) the bar
+    worst = max(rref.check_side(Gi, d["Ji"], d["g"], d["alive"], d["excused"], name + " wi"),
+                rref.check_side(Go, d["Jo"], d["g"], d["alive"], d["excused"], name + " wo"))
+    WORST["harness"] = max(WORST["harness"], worst)
+    print(f"{name}: worst |G - R| / S = {worst:.2e} (so far {WORST['harness']:.2e})")
+    assert (~d["alive"]).sum() == rref.N_DEAD_FIXED
+    assert np.abs(Gi[held]).max() > 0 and np.abs(Go[held]).max() > 0
+
+
+@needs_hipcc
+@pytest.mark.parametrize("name", ["iso", "iso_nojac", "aniso", "aniso_red4", "aniso_uneven"])
+def test_identities(name, tmp_path_factory):
+    """E is homogeneous of degree 0 in wi and in wo: grad . w = 0 within 1e-6 S |w| on both sides (G is the exact gradient rounded to
+    Float component by component: 6e-8 |G| |w|, and |G| <= S up to the bar), and scaling wi by s divides grad_wi by s and leaves
+    grad_wo (s = 0.5 and 4: exact in Float, the unit vectors keep their bits up to the last one), compared to 4 Float ulps of the
+    side's largest component."""
+    d = rref.case_data(name)
+    build, tmp = rref.build_harness(tmp_path_factory), tmp_path_factory.mktemp("rgl_dir_grad_id")
+    sel = np.flatnonzero(d["alive"] & ~d["excused"])[:1024]
+    wi, wo, g = d["wi"][sel], d["wo"][sel], d["g"][sel]
+    Gi, Go, _ = rref.run_harness(build, tmp, d["fields"], wi, wo, g)
+    for G, J, w, side in ((Gi, d["Ji"][sel], wi, "wi"), (Go, d["Jo"][sel], wo, "wo")):
+        _, S = rref.contract(J, g, np.ones(len(sel), bool))
+        G64, w64 = G.astype(np.float64), w.astype(np.float64)
+        assert (np.abs((G64 * w64).sum(-1)) <= 1e-6 * S * np.sqrt((w64 * w64).sum(-1))).all(), side
+        assert np.abs(G64).max() > 0
+    for s in (0.5, 4.0):
+        Si, So, _ = rref.run_harness(build, tmp, d["fields"], wi * np.float32(s), wo, g)
+        for got, want in ((Si.astype(np.float64) * s, Gi.astype(np.float64)), (So.astype(np.float64), Go.astype(np.float64))):
+            assert (np.abs(got - want).max(-1) <= 4 * 2.0 ** -24 * np.abs(want).max(-1)).all(), s
+        Si, So, _ = rref.run_harness(build, tmp, d["fields"], wi, wo * np.float32(s), g)
+        for got, want in ((Si.astype(np.float64), Gi.astype(np.float64)), (So.astype(np.float64) * s, Go.astype(np.float64))):
+            assert (np.abs(got - want).max(-1) <= 4 * 2.0 ** -24 * np.abs(want).max(-1)).all(), s
+
+
+@needs_hipcc
+@pytest.mark.parametrize("name,ops", [("aniso_red2", ((-1, -1, 1),)), ("aniso_red4", ((-1, -1, 1), (-1, 1, 1), (1, -1, 1)))])
+def test_mirror_pairs_of_symmetry_reduced_files_return_mirrored_bits(name, ops, tmp_path_factory):
+    d = rref.case_data(name)
+    build, tmp = rref.build_harness(tmp_path_factory), tmp_path_factory.mktemp("rgl_dir_grad_mirror")
+    Gi, Go, _ = rref.run_harness(build, tmp, d["fields"], d["wi"], d["wo"], d["g"])
+    live = d["alive"]
+    for op in ops:
+        S = np.array(op, np.float32)
+        Mi, Mo, _ = rref.run_harness(build, tmp, d["fields"], d["wi"] * S, d["wo"] * S, d["g"])
+        assert np.array_equal(bits(Mi[live]), bits(Gi[live] * S)) and np.array_equal(bits(Mo[live]), bits(Go[live] * S)), op
+    assert np.abs(Gi[live]).max() > 0
+
+
+@needs_hipcc
+def test_dead_units_are_positive_zero_whatever_g_holds(tmp_path_factory):
+    d = rref.case_data("aniso")
+    dead = ~d["alive"]
+    assert dead.sum() == rref.N_DEAD_FIXED and not np.isfinite(d["g"][dead]).any()
+    Gi, Go, _ = rref.run_harness(rref.build_harness(tmp_path_factory), tmp_path_factory.mktemp("rgl_dir_grad_dead"), d["fields"], d["wi"], d["wo"], d["g"])
+    assert not bits(Gi[dead]).any() and not bits(Go[dead]).any()
+    assert np.isfinite(Gi).all() and np.isfinite(Go).all()
+
+
+# ------------------------------------------------------------------ header, bindings, kernels
+def test_header_declares_and_library_exports_the_rgl_direction_gradient():
+    import ctypes as C
+    from mitsuba_customization_amd import build, host
+    text = open(os.path.join(ROOT, "include", "merl_hip_diff_rgl.h")).read()
+    assert re.search(r'#include\s+"merl_hip_diff.h"', text)
+    code = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    protos = dict(re.findall(r"^[ \t]*int[ \t]+(mrl_\w+)[ \t]*\(([^()]*)\)[ \t]*;", code, flags=re.M))
+    assert set(protos) == set(host.DIFF_RGL_ABI_SYMBOLS) == {"mrl_rgl_grad_dir_batch", "mrl_rgl_grad_dir_queue"}
+    assert host.DIFF_RGL_ABI_SYMBOLS == ("mrl_rgl_grad_dir_batch", "mrl_rgl_grad_dir_queue")
+    others = (host.ABI_SYMBOLS, host.FIT_ABI_SYMBOLS, host.DIFF_ABI_SYMBOLS, host.DIFF_TABLE_ABI_SYMBOLS, host.DIFF_NCH_ABI_SYMBOLS)
+    assert not set(host.DIFF_RGL_ABI_SYMBOLS) & set().union(*map(set, others))
+    for other in ("merl_hip.h", "merl_hip_fit.h", "merl_hip_diff.h", "merl_hip_diff_table.h", "merl_hip_diff_nch.h"):
+        assert "mrl_rgl_grad_dir" not in re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", other)).read(), flags=re.S)
+    for word in ("tot == 0", "1 / |w|", "Not offered", "Symmetry-reduced", "DETERMINISM", "FLT_MAX"):
+        assert word in text
+    build.build_lib()
+    lib = host.load_library()
+
+    def c_class(decl):
+        if "*" in decl or "[" in decl:
+            return "pointer"
+        return {"int": "i32", "int32_t": "i32", "size_t": "u64"}[[w for w in re.findall(r"\w+", decl) if w != "const"][0]]
+
+    def ctypes_class(t):
+        return "pointer" if t is C.c_void_p else {C.c_int32: "i32", C.c_uint64: "u64"}[t]
+    want = {"mrl_rgl_grad_dir_batch": ["pointer"] * 5 + ["i32", "u64", "pointer", "pointer"],
+            "mrl_rgl_grad_dir_queue": ["pointer"] * 5 + ["i32", "pointer", "pointer", "u64", "pointer", "pointer"]}
+    for name in host.DIFF_RGL_ABI_SYMBOLS:
+        assert hasattr(lib, name)
+        assert [c_class(p) for p in protos[name].split(",")] == want[name]
+        assert [ctypes_class(t) for t in getattr(lib, name).argtypes] == want[name]
+    assert lib.mrl_rgl_grad_dir_batch(None, None, None, None, None, 0, 4, None, None) == -1            # no context: MRL_ERR_INVALID
+    assert lib.mrl_rgl_grad_dir_queue(None, None, None, None, None, 0, None, None, 4, None, None) == -1
+
+
+def kernel_resources():
+    """{kernel name: (scratch bytes per lane, VGPRs, AGPRs)} of the kernel's translation unit, from the compiler's resource-usage remarks"""
+    r = subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                        "-c", "-o", os.devnull, rref.KERNEL_SOURCE], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    vgprs = [int(v) for v in re.findall(r" VGPRs: (\d+)", r.stderr)]
+    agprs = [int(v) for v in re.findall(r"AGPRs: (\d+)", r.stderr)] or [0] * len(vgprs)
+    assert len(names) == len(scratch) == len(vgprs) == len(agprs)
+    demangled = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines()
+    return {d.replace("mrl::(anonymous namespace)::", "").replace("void ", "").split("(")[0]: (s, v, a)
+            for d, s, v, a in zip(demangled, scratch, vgprs, agprs) if "k_rgl_dir_grad<" in d}
+
+
+@needs_hipcc
+def test_single_material_kernels_compile_for_gfx950_without_scratch():
+    """The kernels of a launch without material ids (MULTI = false: one per bracket shape) use no scratch; every kernel of the file
+    fits the launch shape it is given."""
+    text = open(rref.KERNEL_SOURCE).read()
+    block = int(re.search(r"constexpr int kRglDirBlock = (\d+);", text).group(1))
+    per_cu = {False: int(re.search(r"#define MRL_RGL_DIR_BLOCKS_PER_CU (\d+)", text).group(1)),
+              True: int(re.search(r"#define MRL_RGL_DIR_BLOCKS_PER_CU_15 (\d+)", text).group(1))}
+    assert "mask == 15 || mask == 0 ? MRL_RGL_DIR_BLOCKS_PER_CU_15 : MRL_RGL_DIR_BLOCKS_PER_CU" in text
+    kernels = kernel_resources()
+    want = {f"k_rgl_dir_grad<{i}, false, {m}>" for i in ("false", "true") for m in (1, 3, 5, 15)} | {f"k_rgl_dir_grad<{i}, true, 0>" for i in ("false", "true")}
+    assert set(kernels) == want, sorted(kernels)
+    for name, (s, v, a) in sorted(kernels.items()):
+        blocks = per_cu[name.endswith(" 15>") or name.endswith(" 0>")]
+        waves_per_simd = min(8, 512 // ((v + a + 7) // 8 * 8))
+        print(f"{name}: {v} VGPRs + {a} AGPRs, {s} B of scratch per lane, {waves_per_simd} waves per SIMD, {blocks} blocks of {block} per compute unit")
+        assert blocks * (block // 64) <= 4 * waves_per_simd, (name, v, a)
+        if ", false, " in name:
+            assert s == 0, (name, s)
