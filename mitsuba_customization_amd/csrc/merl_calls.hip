@@ -267,12 +267,24 @@ int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f)
     if (c.n == 0) return MRL_OK;
     if (c.queued && (!c.queue || !c.queue_count)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
     StreamList streams = { { (void *)c.wi, 12, false, "wi" }, { (void *)c.wo, 12, false, "wo" }, { (void *)c.g, f.g_bytes, false, f.g_name } };
+    for (const DirGradExtra &x : c.extra) if (x.required) streams.push_back({ x.ptr, x.unit_bytes, x.out, x.name });
     if (first_null(streams)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    if (!c.grad_wi && !c.grad_wo) return fail(ctx, MRL_ERR_INVALID, "grad_wi and grad_wo are both null");
+    streams.resize(3);
+    bool any_out = c.grad_wi || c.grad_wo;
+    for (const DirGradExtra &x : c.extra) any_out = any_out || (x.out && x.ptr);
+    if (!any_out) return fail(ctx, MRL_ERR_INVALID, c.extra.empty() ? "grad_wi and grad_wo are both null" : "every output is null");
     int at_mat = -1, at_wi = -1, at_wo = -1;
     if (c.mat) { at_mat = (int)streams.size(); streams.push_back({ (void *)c.mat, 4, false, "mat" }); }
     if (c.grad_wi) { at_wi = (int)streams.size(); streams.push_back({ c.grad_wi, 12, true, "grad_wi" }); }
     if (c.grad_wo) { at_wo = (int)streams.size(); streams.push_back({ c.grad_wo, 12, true, "grad_wo" }); }
+    // the extra streams the call goes with: listed, so that they take part in the pointer kind and in the chunks of host arrays
+    std::vector<int> at_extra(c.extra.size(), -1);
+    std::vector<void *> extra(c.extra.size(), nullptr);
+    for (size_t k = 0; k < c.extra.size(); ++k) {
+        const DirGradExtra &x = c.extra[k];
+        extra[k] = x.ptr;
+        if (x.ptr) { at_extra[k] = (int)streams.size(); streams.push_back({ x.ptr, x.unit_bytes, x.out, x.name }); }
+    }
     if (ctx->materials.empty()) return fail(ctx, MRL_ERR_MATERIAL, "no material loaded");
     if (!c.mat) {
         if (c.single_id < 0 || (size_t)c.single_id >= ctx->materials.size() || ctx->materials[(size_t)c.single_id].released)
@@ -297,13 +309,15 @@ int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f)
     a.idx = c.queue; a.idx_count = c.queue_count;
     if (kind == 1) {
         a.wi = c.wi; a.wo = c.wo; a.mat = c.mat; a.n = c.n;
-        MRL_HIP(ctx, f.launch(a, c.g, c.grad_wi, c.grad_wo));
+        MRL_HIP(ctx, f.launch(a, c.g, c.grad_wi, c.grad_wo, extra.empty() ? nullptr : extra.data()));
         return MRL_OK;
     }
-    return run_host_staged(ctx, streams, c.n, 0, [&](char *const *addr, size_t m) -> int {
+    return run_host_staged(ctx, streams, c.n, f.cap_bytes, [&](char *const *addr, size_t m) -> int {
         a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.n = m;
         a.mat = at_mat >= 0 ? (const int32_t *)addr[at_mat] : nullptr;
-        MRL_HIP(ctx, f.launch(a, (const float *)addr[2], at_wi >= 0 ? (float *)addr[at_wi] : nullptr, at_wo >= 0 ? (float *)addr[at_wo] : nullptr));
+        for (size_t k = 0; k < extra.size(); ++k) extra[k] = at_extra[k] >= 0 ? addr[at_extra[k]] : nullptr;
+        MRL_HIP(ctx, f.launch(a, (const float *)addr[2], at_wi >= 0 ? (float *)addr[at_wi] : nullptr, at_wo >= 0 ? (float *)addr[at_wo] : nullptr,
+                              extra.empty() ? nullptr : extra.data()));
         return MRL_OK;
     });
 }

@@ -212,6 +212,14 @@ using HostLaunch = std::function<int(char *const *addr, size_t m)>;
 int run_host_staged(mrl_ctx *ctx, const StreamList &streams, size_t n, size_t cap_bytes, const HostLaunch &launch);
 
 // A direction-gradient call (include/merl_hip_diff*.h), whole arrays or a queue, and what its family of materials supplies
+// a further per-unit array of a direction-gradient call (the spectral RGL gradient: wavelengths in, grad_wavelengths out)
+struct DirGradExtra {
+    void *ptr;                                   // null: the call goes without it — unless `required`
+    size_t unit_bytes;
+    bool out;                                    // an output counts among the outputs of which one must be given
+    const char *name;
+    bool required;                               // null is MRL_ERR_INVALID ("null array argument")
+};
 struct DirGradCall {
     const float *wi, *wo, *g;
     const int32_t *mat;
@@ -219,7 +227,8 @@ struct DirGradCall {
     size_t n;                                    // units; queued: the queue's capacity
     bool queued;
     const uint32_t *queue, *queue_count;
-    float *grad_wi, *grad_wo;                    // either may be null, not both
+    float *grad_wi, *grad_wo;                    // either may be null; one output (an `out` extra counts) must be given
+    std::vector<DirGradExtra> extra = {};        // in the order the family's launch receives their addresses
 };
 struct DirGradFamily {
     size_t g_bytes;                              // of g per unit
@@ -228,8 +237,10 @@ struct DirGradFamily {
     std::string not_evaluated;                   // the MRL_ERR_MATERIAL message if it is not
     bool refuses_renormalise;                    // MRL_OPT_NEGATIVE = renormalise: MRL_ERR_INVALID
     std::function<mrl::MaterialDev()> single_with_ids;       // BatchArgs::single of a launch with ids: what a unit of another id reads
-    // the family's kernel on device-accessible arrays; a: everything but the outputs
-    std::function<hipError_t(const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo)> launch;
+    // the family's kernel on device-accessible arrays; a: everything but the outputs; extra: one address per DirGradCall::extra
+    // entry (null where the call goes without it; nullptr itself when the call lists none)
+    std::function<hipError_t(const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo, void *const *extra)> launch;
+    size_t cap_bytes = 0;                        // host arrays: > 0, chunks so small that the staging slot stays below it
 };
 // checks in the order the headers document, then f.launch on the caller's device arrays or chunk by chunk on staged host arrays
 int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f);

@@ -88,7 +88,7 @@ int ggx_grad_dir(mrl_ctx *ctx, const DirGradCall &c)
     return grad_dir_call(ctx, c, { 12, "grad_rgb",
         [](const MaterialHost &m) { return m.dev.kind == mrl::KIND_GGX; }, "the direction gradient is defined for GGX conductor materials", false,
         constant_ggx,
-        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo) {
+        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo, void *const *) {
             return mrl::launch_ggx_grad_dir(a, { g, grad_wi, grad_wo }, ctx->compute_units, ctx->stream);
         } });
 }

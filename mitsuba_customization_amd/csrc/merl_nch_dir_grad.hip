@@ -106,7 +106,7 @@ int nch_grad_dir(mrl_ctx *ctx, const DirGradCall &c, int n_ch)
             no_table = safe == ctx->materials.end();
             return no_table ? tombstone_dev(ctx) : safe->dev;
         },
-        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo) {
+        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo, void *const *) {
             return mrl::launch_table_grad_dir_nch(a, { g, grad_wi, grad_wo }, n_ch, no_table, ctx->compute_units, ctx->stream);
         } });
 }

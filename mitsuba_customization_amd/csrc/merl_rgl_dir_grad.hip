@@ -96,7 +96,7 @@ int rgl_grad_dir(mrl_ctx *ctx, const DirGradCall &c)
         [](const MaterialHost &m) { return m.dev.kind == mrl::KIND_RGL; },
         "the RGL direction gradient is defined for RGB RGL materials (mrl_material_upload_rgl / mrl_material_load_rgl)", false,
         [&] { return tombstone_dev(ctx); },
-        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo) {
+        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo, void *const *) {
             const mrl::RglDev r = a.mat ? mrl::RglDev{} : ctx->materials[(size_t)c.single_id].rgl;
             return mrl::launch_rgl_dir_grad(a, { g, grad_wi, grad_wo }, r, ctx->compute_units, ctx->stream);
         } });

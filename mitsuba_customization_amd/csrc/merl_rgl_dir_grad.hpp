@@ -20,6 +20,8 @@
 // nothing is summed before its stage's reads are out.  (sx, sy) are formed with warp_invert's own expressions, so the rgb cell is
 // eval's to the bit.  Where a map has no derivative (m at the normal, wi at the normal) that angle's terms are dropped by a select
 // BEFORE any product.  Contraction is off and the FMAs are spelt out: a unit's bits do not depend on the kernel it is inlined into.
+// Everything but step 1's channels is dir_grad_core, which the spectral function shares (merl_rgl_spectral_dir_grad.hpp, DESIGN.md
+// §5q): the channel stage is a callable that fills ChannelSums; eval_dir_grad passes the three RGB channels.
 #pragma once
 #include "merl_rgl.hpp"
 #include "merl_table_dir_grad.hpp"      // through_normalisation, finite_f32, kSingular
@@ -111,27 +113,60 @@ MRL_HD void pull_angles(const Vec3d &v, double rho2, bool ok, double tb, double 
     out[0] = __builtin_fma(-pr, v.y, hz * v.x); out[1] = __builtin_fma(pr, v.x, hz * v.y); out[2] = -(c * rho);
 }
 
-// grad_wi = sum_c g_c dE_c / d wi and grad_wo of ONE unit on the RGB RGL material b; g: where its parameter grids are read.  Dead
-// units — eval's: wi.z <= 0, wo.z <= 0, a NaN / inf component, a failed normalisation — return +0.0f before anything is read,
-// whatever g32 holds.  MASK: the bracket shape when the caller knows it at compile time (1, 3, 5, 15: find_slices' mask; every test
-// on it folds and the reads and sums are straight-line code), 0: tested at run time — the same operations in the same order either way.
-template <int MASK = 0, class Grids>
-MRL_HD RglDirGrad eval_dir_grad(const RglDev &b, const Grids &g, float wix, float wiy, float wiz, float wox, float woy, float woz, const float g32[3])
+// the partials of W = sum_k g_k V_k the channel stage hands back: in the rgb cell's fractions and in (tp, tt)
+struct ChannelSums { double W, W_fx, W_fy, W_tp, W_tt; };
+// one channel (an RGB channel, a wavelength node) at the cell c under the three sets of weights: its value and its four partials
+struct NodeTerms { double v, fx, fy, tp, tt; };
+MRL_HD NodeTerms node_terms(const Slices &sv, const Slices &sp, const Slices &st, const Cell &c, const Raw4 &raw)
 {
 #pragma clang fp contract(off)
-    RglDirGrad out;
+    NodeTerms n;
+    n.v = bilinear(blend4(sv, raw), c.fx, c.fy);
+    const CellDiff d = cell_diff(sv, raw);
+    n.tp = bilinear(blend4(sp, raw), c.fx, c.fy); n.tt = bilinear(blend4(st, raw), c.fx, c.fy);
+    n.fx = lerp(c.fy, d.xl, d.xu); n.fy = lerp(c.fx, d.yl, d.yr);
+    return n;
+}
+// ... joins the sums with the cotangent gk (0 where the channel is clamped): one ascending FMA chain per sum
+MRL_HD void add_channel(ChannelSums &a, double gk, const NodeTerms &n)
+{
+#pragma clang fp contract(off)
+    a.W = __builtin_fma(gk, n.v, a.W);
+    a.W_fx = __builtin_fma(gk, n.fx, a.W_fx);
+    a.W_fy = __builtin_fma(gk, n.fy, a.W_fy);
+    a.W_tp = __builtin_fma(gk, n.tp, a.W_tp);
+    a.W_tt = __builtin_fma(gk, n.tt, a.W_tt);
+}
+// a channel whose value is one stored channel's: clamped below 0
+MRL_HD void channel_term(ChannelSums &a, const Slices &sv, const Slices &sp, const Slices &st, const Cell &c, const Raw4 &raw, float g)
+{
+    const NodeTerms n = node_terms(sv, sp, st, c, raw);
+    add_channel(a, n.v < 0.0 ? 0.0 : (double)g, n);
+}
+
+// The gradient of ONE unit on the RGL material b in everything but its channel stage — shared by the RGB function below and the
+// spectral one (merl_rgl_spectral_dir_grad.hpp).  channels(wr, c, sv, sp, st, scale, sums): reads the measured values at the cell c
+// of the values table wr under the weights sv (value), sp, st (d / d tp, d / d tt) and fills sums; scale: ndf / (4 sigma), or 1.
+// false: a dead unit — eval's: wi.z <= 0, wo.z <= 0, a NaN / inf component, a failed normalisation —, out is +0.0f, nothing was read
+// and channels was not called.  g: where the parameter grids are read.  MASK: the bracket shape when the caller knows it at compile
+// time (1, 3, 5, 15: find_slices' mask; every test on it folds and the reads and sums are straight-line code), 0: tested at run time
+// — the same operations in the same order either way.
+template <int MASK, class Grids, class Channels>
+MRL_HD bool dir_grad_core(const RglDev &b, const Grids &g, float wix, float wiy, float wiz, float wox, float woy, float woz, RglDirGrad &out, Channels &&channels)
+{
+#pragma clang fp contract(off)
     for (int k = 0; k < 3; ++k) out.wi[k] = out.wo[k] = 0.0f;
     const float nf = ((wix - wix) + (wiy - wiy)) + ((wiz - wiz) + (wox - wox)) + ((woy - woy) + (woz - woz));      // 0, or NaN
-    if (!(wiz > 0.0f) || !(woz > 0.0f) || !(nf == 0.0f)) return out;
+    if (!(wiz > 0.0f) || !(woz > 0.0f) || !(nf == 0.0f)) return false;
     Incident in;
-    if (!incident<false>(b, g, wix, wiy, wiz, in)) return out;
+    if (!incident<false>(b, g, wix, wiy, wiz, in)) return false;
     if constexpr (MASK != 0) in.sv.mask = MASK;
     const Vec3d &a = in.wi;
     Vec3d wo = { (double)(wox * in.fx), (double)(woy * in.fy), (double)woz };
-    if (!unit3(wo)) return out;
+    if (!unit3(wo)) return false;
     const Vec3d s = { a.x + wo.x, a.y + wo.y, a.z + wo.z };
     Vec3d m = s;
-    if (!unit3(m)) return out;
+    if (!unit3(m)) return false;
     // half_lookup's coordinates
     const double theta_m = elevation(m), phi_m = azimuth(m.y, m.x);
     const double umx = theta2u(theta_m);
@@ -212,26 +247,12 @@ MRL_HD RglDirGrad eval_dir_grad(const RglDev &b, const Grids &g, float wix, floa
         s_y = sg_b * lerp(cs.fx, ds.yl, ds.yr) * (double)(ws.ny - 1);
     }
 
-    // ---- stage 2: the three channels at the cell of (sx, sy) ----
+    // ---- stage 2: the channels at the cell of (sx, sy) ----
+    // 1. the partials of W = sum_k g_k V_k over the channels that are not clamped
     const Cell c = locate(wr, sx, sy);
-    Raw4 raw0 = fetch_raw(sv, wr, c.index, 0), raw1 = fetch_raw(sv, wr, c.index, 1), raw2 = fetch_raw(sv, wr, c.index, 2);
-
-    // 1. the partials of W = sum_c g_c V_c over the channels that are not clamped
-    double W = 0.0, W_fx = 0.0, W_fy = 0.0, W_tp = 0.0, W_tt = 0.0;
-    auto channel = [&](const Raw4 &raw, float g) {
-        const double v = bilinear(blend4(sv, raw), c.fx, c.fy);
-        const CellDiff d = cell_diff(sv, raw);
-        const double v_tp = bilinear(blend4(sp, raw), c.fx, c.fy), v_tt = bilinear(blend4(st, raw), c.fx, c.fy);
-        const double gk = v < 0.0 ? 0.0 : (double)g;
-        W = __builtin_fma(gk, v, W);
-        W_fx = __builtin_fma(gk, lerp(c.fy, d.xl, d.xu), W_fx);
-        W_fy = __builtin_fma(gk, lerp(c.fx, d.yl, d.yr), W_fy);
-        W_tp = __builtin_fma(gk, v_tp, W_tp);
-        W_tt = __builtin_fma(gk, v_tt, W_tt);
-    };
-    not_before_here(raw0); channel(raw0, g32[0]);
-    not_before_here(raw1); channel(raw1, g32[1]);
-    not_before_here(raw2); channel(raw2, g32[2]);
+    ChannelSums cs_ = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    channels(wr, c, sv, sp, st, scale, cs_);
+    const double W = cs_.W, W_fx = cs_.W_fx, W_fy = cs_.W_fy, W_tp = cs_.W_tp, W_tt = cs_.W_tt;
     double umx_b = W * n_x, umy_b = W * n_y;
     const double uix_b = W * s_x, uiy_b = W * s_y;
 
@@ -264,6 +285,22 @@ MRL_HD RglDirGrad eval_dir_grad(const RglDev &b, const Grids &g, float wix, floa
     const double fx = (double)in.fx, fy = (double)in.fy;
     out.wi[0] = fast::finite_f32(gi[0] * fx); out.wi[1] = fast::finite_f32(gi[1] * fy); out.wi[2] = fast::finite_f32(gi[2]);
     out.wo[0] = fast::finite_f32(go[0] * fx); out.wo[1] = fast::finite_f32(go[1] * fy); out.wo[2] = fast::finite_f32(go[2]);
+    return true;
+}
+
+// grad_wi = sum_c g_c dE_c / d wi and grad_wo of ONE unit on the RGB RGL material b: dir_grad_core with the three channels' corner
+// vectors read together and summed in channel order.  Dead units return +0.0f whatever g32 holds.
+template <int MASK = 0, class Grids>
+MRL_HD RglDirGrad eval_dir_grad(const RglDev &b, const Grids &g, float wix, float wiy, float wiz, float wox, float woy, float woz, const float g32[3])
+{
+    RglDirGrad out;
+    dir_grad_core<MASK>(b, g, wix, wiy, wiz, wox, woy, woz, out,
+        [&](const WarpDev &wr, const Cell &c, const Slices &sv, const Slices &sp, const Slices &st, double, ChannelSums &a) {
+            Raw4 raw0 = fetch_raw(sv, wr, c.index, 0), raw1 = fetch_raw(sv, wr, c.index, 1), raw2 = fetch_raw(sv, wr, c.index, 2);
+            not_before_here(raw0); channel_term(a, sv, sp, st, c, raw0, g32[0]);
+            not_before_here(raw1); channel_term(a, sv, sp, st, c, raw1, g32[1]);
+            not_before_here(raw2); channel_term(a, sv, sp, st, c, raw2, g32[2]);
+        });
     return out;
 }
 

@@ -82,7 +82,7 @@ int table_grad_dir(mrl_ctx *ctx, const DirGradCall &c)
         [](const MaterialHost &m) { return m.dev.kind == mrl::KIND_MERL || m.dev.kind == mrl::KIND_TABLE; },
         "the table direction gradient is defined for RGB table materials (MERL / customized_measurement)", true,
         [&] { return tombstone_dev(ctx); },
-        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo) {
+        [&](const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo, void *const *) {
             return mrl::launch_table_grad_dir(a, { g, grad_wi, grad_wo }, ctx->table_layout, ctx->compute_units, ctx->stream);
         } });
 }

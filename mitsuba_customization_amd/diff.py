@@ -10,6 +10,8 @@ the gradient has flowed through eval into whatever produced wi and wo — a shad
 gradient in the material's own parameters is MerlHip.ggx_grad, in a table's texels MerlHip.table_grad (fit.py).  table_eval is the
 same on a table material, rgl_eval on an RGL material, and eval serves every one of these kinds and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
 tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels].
+rgl_spectral_eval is MerlHip.eval_spectral on spectral RGL materials (include/merl_hip_diff_rgl_spectral.h,
+mrl_rgl_grad_dir_spectral_batch): [n, W] values at per-unit wavelengths, differentiable in the wavelengths as well.
 
 tables= and params= make the same calls differentiable in the MATERIAL as well: the table tensor(s) behind table
 materials, the 7 parameters behind GGX conductors.  Forward writes a tensor's current values into its resident material in place
@@ -84,6 +86,29 @@ class _Eval(torch.autograd.Function):
         needed = [i for i, need in enumerate(ctx.needs_input_grad[5:]) if need]
         in_values = ctx.material_call(wi, wo, g, needed) if needed else [None] * ctx.n_values
         return (grads.get("wi"), grads.get("wo"), None, None, None, *in_values)
+
+
+class _SpectralEval(torch.autograd.Function):
+    """_Eval's sibling with a third differentiable input, the per-unit wavelengths [n, W]: forward_call(wi, wo, wavelengths) is a
+    spectral eval of the host, backward_call(wi, wo, wavelengths, grad, want=) its gradient for a subset of ("wi", "wo",
+    "wavelengths")"""
+    @staticmethod
+    def forward(ctx, wi, wo, wavelengths, forward_call, backward_call):
+        wi, wo, wavelengths = wi.contiguous(), wo.contiguous(), wavelengths.contiguous()
+        ctx.save_for_backward(wi, wo, wavelengths)
+        ctx.backward_call = backward_call
+        return forward_call(wi, wo, wavelengths)
+
+    @staticmethod
+    def backward(ctx, grad_values):
+        wi, wo, wavelengths = ctx.saved_tensors
+        # only what the graph asks for: the other output pointers are NULL and those gradients are neither computed nor written
+        want = tuple(name for name, needed in zip(("wi", "wo", "wavelengths"), ctx.needs_input_grad[:3]) if needed)
+        grads = {}
+        if want:
+            out = ctx.backward_call(wi, wo, wavelengths, grad_values.contiguous(), want=want)
+            grads = dict(zip(want, (out,) if len(want) == 1 else out))
+        return (grads.get("wi"), grads.get("wo"), grads.get("wavelengths"), None, None)
 
 
 class _Materials:
@@ -191,11 +216,29 @@ def rgl_eval(ctx, wi, wo, mat=None, material: int = 0):
                   mat, material)
 
 
+def rgl_spectral_eval(ctx, wi, wo, wavelengths, mat=None, material: int = 0):
+    """MerlHip.eval_spectral(wi, wo, wavelengths, material) — with mat=, eval_spectral_mat — of the context `ctx`: [n, W] values at the
+    per-unit wavelengths [n, W] (float32 device tensor), differentiable in wi, wo AND the wavelengths.  The materials must be
+    spectral RGL materials (upload_rgl of a file with "spectra"): the backward pass of a single material of another kind raises
+    MRL_ERR_MATERIAL, and with mat= a unit whose id names no live spectral RGL material receives zero gradients.  Backward is one
+    MerlHip.rgl_grad_dir_spectral call for what the graph needs (include/merl_hip_diff_rgl_spectral.h): the exact gradient of the
+    piecewise function in the cells and the wavelength bracket eval selects; d value / d wavelength is piecewise constant, 0 outside
+    the file's nodes and where the value is clamped.  The file's values are not differentiable."""
+    if wavelengths is None:
+        raise ValueError("rgl_spectral_eval: per-unit wavelengths [n, W] (the file's own nodes are no differentiable input)")
+    if mat is None:
+        forward = lambda a, b, wl: ctx.eval_spectral(a, b, wl, material)
+    else:
+        forward = lambda a, b, wl: ctx.eval_spectral_mat(a, b, wl, mat)
+    return _SpectralEval.apply(wi, wo, wavelengths, forward, partial(ctx.rgl_grad_dir_spectral, mat=mat, material=material))
+
+
 def eval(ctx, wi, wo, mat=None, material: int = 0, tables=None, params=None):
     """MerlHip.eval(wi, wo, mat, material), differentiable in wi and wo, for GGX conductors, RGB tables, RGB RGL materials and batches
     that mix them.  Single material: the backward pass is the gradient call of that material's kind.  With mat=: the sum of
     table_grad_dir and ggx_grad_dir — and of rgl_grad_dir when the context holds a live RGB RGL material —, each exactly zero on the
-    others' units; units of kinds with no gradient (n-channel, spectral RGL, released or unknown ids) receive zeros.
+    others' units; units of kinds this RGB-wide call does not serve (n-channel tables, spectral RGL materials — their values are
+    [n, W]: rgl_spectral_eval() is their differentiable eval —, released or unknown ids) receive zeros.
     tables= / params=: as in table_eval() and ggx_eval(), for the tables and the conductors of a mixed batch."""
     return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(_any_backward, ctx, mat=mat, material=material),
                   mat, material, tables=tables, params=params)

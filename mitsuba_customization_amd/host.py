@@ -76,6 +76,8 @@ DIFF_TABLE_ABI_SYMBOLS = ("mrl_table_grad_dir_batch", "mrl_table_grad_dir_queue"
 DIFF_NCH_ABI_SYMBOLS = ("mrl_table_grad_dir_batch_nch", "mrl_table_grad_dir_queue_nch")
 # every symbol include/merl_hip_diff_rgl.h declares: the same gradient on RGB RGL materials
 DIFF_RGL_ABI_SYMBOLS = ("mrl_rgl_grad_dir_batch", "mrl_rgl_grad_dir_queue")
+# every symbol include/merl_hip_diff_rgl_spectral.h declares: the direction and wavelength gradient on spectral RGL materials
+DIFF_RGL_SPECTRAL_ABI_SYMBOLS = ("mrl_rgl_grad_dir_spectral_batch", "mrl_rgl_grad_dir_spectral_queue")
 # every symbol include/merl_hip_fit_table.h declares: the table adjoint with a material id per unit and over wavefront queues
 FIT_TABLE_ABI_SYMBOLS = ("mrl_table_grad_batch_mat", "mrl_table_grad_queue", "mrl_table_grad_layout")
 TABLE_GRAD_MAX_TARGETS = 16         # MRL_TABLE_GRAD_MAX_TARGETS
@@ -313,6 +315,8 @@ def load_library(path: Optional[str] = None):
     L.mrl_table_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
     L.mrl_rgl_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_rgl_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
+    L.mrl_rgl_grad_dir_spectral_batch.argtypes = [vp, fp, fp, fp, C.c_int32, fp, vp, C.c_int32, C.c_size_t, fp, fp, fp]
+    L.mrl_rgl_grad_dir_spectral_queue.argtypes = [vp, fp, fp, fp, C.c_int32, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp, fp]
     L.mrl_table_grad_dir_batch_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, C.c_int, fp, fp]
     L.mrl_table_grad_dir_queue_nch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, C.c_int, fp, fp]
     L.mrl_generate_pairs.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, fp, fp, fp]
@@ -1075,6 +1079,53 @@ class MerlHip:
         id names no live RGB RGL material, gets zeros.  Same conventions as ggx_grad_dir()."""
         return self._grad_dir_call("mrl_rgl_grad_dir_batch", wi, wo, grad_rgb, mat, material, want, out)
 
+    def _grad_dir_spectral_call(self, symbol, wi, wo, wavelengths, g, mat, material, n_wavelengths, want, out, queue=None):
+        """One spectral direction-gradient call, the sibling of _grad_dir_call with the two extra per-unit arrays.  want: a subset of
+        ("wi", "wo", "wavelengths") in that order; out: one array, or a tuple in want's order.  Returns the gradient wanted, or the
+        tuple."""
+        names = ("wi", "wo", "wavelengths")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in names for w in want) or list(want) != [w for w in names if w in want]:
+            raise ValueError('want: a non-empty subset of ("wi", "wo", "wavelengths"), in that order')
+        n = int(wi.shape[0])
+        if wavelengths is None:
+            if n_wavelengths is None:
+                raise ValueError("n_wavelengths: needed without a wavelength array (the number of the file's nodes)")
+            W = int(n_wavelengths)
+        else:
+            W = int(wavelengths.shape[1])
+            if n_wavelengths is not None and int(n_wavelengths) != W:
+                raise ValueError(f"n_wavelengths = {n_wavelengths}, but wavelengths has {W} columns")
+        if queue is None:
+            self._prep(wi)
+        middle = (n,) if queue is None else self._queue(wi, *queue)
+        alloc = self._empty if queue is None else self._zeros
+        shapes = {"wi": (n, 3), "wo": (n, 3), "wavelengths": (n, W)}
+        if out is None:
+            outs = tuple(alloc(wi, shapes[w]) for w in want)
+        else:
+            outs = (out,) if len(want) == 1 and not isinstance(out, (tuple, list)) else tuple(out)
+            if len(outs) != len(want):
+                raise ValueError(f"out: {len(want)} arrays wanted, got {len(outs)}")
+        by_name = dict(zip(want, outs))
+        cols = max(W, 1)
+        self._check(getattr(self._lib, symbol)(self._ctx, _addr(wi, np.float32, 3, n, "wi"), _addr(wo, np.float32, 3, n, "wo"),
+                                               _addr(wavelengths, np.float32, cols, n, "wavelengths"), W, _addr(g, np.float32, cols, n, "grad_values"),
+                                               _addr(mat, np.int32, None, n, "mat"), material, *middle,
+                                               _addr(by_name.get("wi"), np.float32, 3, n, "grad_wi"), _addr(by_name.get("wo"), np.float32, 3, n, "grad_wo"),
+                                               _addr(by_name.get("wavelengths"), np.float32, cols, n, "grad_wavelengths")), symbol)
+        return outs[0] if len(outs) == 1 else outs
+
+    def rgl_grad_dir_spectral(self, wi, wo, wavelengths, grad_values, mat=None, material: int = 0, n_wavelengths: Optional[int] = None,
+                              want=("wi", "wo"), out=None):
+        """The gradient of eval_spectral on spectral RGL materials (mrl_rgl_grad_dir_spectral_batch,
+        include/merl_hip_diff_rgl_spectral.h): per unit grad_wi = sum_k grad_values_k d E_k / d wi and the same in wo, [n, 3] f32, and
+        with "wavelengths" in want grad_wavelengths [n, W] = grad_values_k d E_k / d lambda_k; all overwritten.  wavelengths: [n, W]
+        f32, or None for the file's own nodes (n_wavelengths = their number; without mat= and without "wavelengths" in want).  A dead
+        unit, and with mat= a unit whose id names no live spectral RGL material, gets zeros.  numpy in -> numpy out, device tensors
+        in -> device tensors out.  Returns the gradient wanted, or a tuple in want's order."""
+        return self._grad_dir_spectral_call("mrl_rgl_grad_dir_spectral_batch", wi, wo, wavelengths, grad_values, mat, material, n_wavelengths, want, out)
+
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
 
@@ -1156,6 +1207,13 @@ class MerlHip:
         """rgl_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_rgl_grad_dir_queue); other slots of `out` stay as they
         are (outputs allocated here start from zeros)."""
         return self._grad_dir_call("mrl_rgl_grad_dir_queue", wi, wo, grad_rgb, mat, material, want, out, queue=(queue, count, capacity))
+
+    def rgl_grad_dir_spectral_queue(self, wi, wo, wavelengths, grad_values, queue, count, mat=None, material: int = 0, capacity=None,
+                                    n_wavelengths: Optional[int] = None, want=("wi", "wo"), out=None):
+        """rgl_grad_dir_spectral() of the slots queue[0 .. min(count, capacity)) (mrl_rgl_grad_dir_spectral_queue); other slots of
+        `out` stay as they are (outputs allocated here start from zeros)."""
+        return self._grad_dir_spectral_call("mrl_rgl_grad_dir_spectral_queue", wi, wo, wavelengths, grad_values, mat, material, n_wavelengths, want, out,
+                                            queue=(queue, count, capacity))
 
     def table_grad_dir_queue_nch(self, wi, wo, grad_values, queue, count, n_channels: int, mat=None, material: int = 0, capacity=None,
                                  want=("wi", "wo"), out=None):
