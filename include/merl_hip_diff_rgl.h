@@ -60,8 +60,9 @@ extern "C" {
  * material-id, queue and host-array forms return identical bits for the same unit, whatever n, the grid or the unit's position;
  * grad_wi has the same bits with and without grad_wo.  Contraction is off and the FMAs are explicit in the per-unit function; no
  * kernel is compiled for one bracket shape.
- * Not offered: device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample, and the table
- * adjoint on RGL files (fitting a file's values).  Spectral RGL files: merl_hip_diff_rgl_spectral.h. */
+ * Not offered: device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample.  The gradient in an
+ * RGB file's measured values (fitting a file) is mrl_rgl_values_grad_batch / _queue of merl_hip_fit_rgl.h.  Spectral RGL files:
+ * merl_hip_diff_rgl_spectral.h. */
 int mrl_rgl_grad_dir_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                            const int32_t *mat, int32_t single_id, size_t n,
                            float *grad_wi, float *grad_wo);

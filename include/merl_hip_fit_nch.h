@@ -53,7 +53,7 @@ extern "C" {
  * together before they reach memory only when they share target and cell.
  * MRL_OPT_TABLE_GRAD_KERNEL: 0 auto (lanes of a wave that share a cell are summed first when at least four share the first live
  * lane's), 2 never, 3 always.  Value 1, the plain planar form of the RGB calls, is not built for n-channel tables: it behaves as 2.
- * Not offered: device groups (mrl_group_*), RGL materials, the one-unit paths.  (An autograd wrapper that returns a table gradient:
+ * RGB RGL materials: merl_hip_fit_rgl.h.  Not offered: device groups (mrl_group_*), spectral RGL materials, the one-unit paths.  (An autograd wrapper that returns a table gradient:
  * diff.table_eval_nch(tables=), over mrl_material_update_table of merl_hip_update.h.) */
 int mrl_table_grad_batch_nch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_values,
                              const int32_t *mat, int32_t single_id, size_t n, int n_channels,

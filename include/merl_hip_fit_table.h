@@ -50,7 +50,7 @@ extern "C" {
  * Accuracy: as mrl_table_grad_batch — the sums are f64 atomics in no fixed order: two calls agree to f64 rounding, not bit for bit.
  * Two units are added together before they reach memory only when they share target and cell.  All four
  * MRL_OPT_TABLE_GRAD_KERNEL values serve these calls and give the same sums up to f64 rounding.
- * n-channel tables: merl_hip_fit_nch.h.  Not offered: device groups (mrl_group_*), RGL materials, the one-unit paths.  The GGX parameter gradient with
+ * n-channel tables: merl_hip_fit_nch.h.  RGB RGL materials: merl_hip_fit_rgl.h.  Not offered: device groups (mrl_group_*), the one-unit paths.  The GGX parameter gradient with
  * ids and over queues is mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue of merl_hip_fit_ggx.h. */
 int mrl_table_grad_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                              const int32_t *mat, int32_t single_id, size_t n,

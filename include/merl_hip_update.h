@@ -50,7 +50,8 @@ extern "C" {
  * Refused with MRL_ERR_MATERIAL, the material untouched: a GGX, RGL or spectral material; a released, negative or out-of-range id; a
  * table restored from an image file (it carries no channel scales — the table adjoint refuses it for the same reason).
  * MRL_ERR_INVALID: NULL planar, unknown flag bits.
- * Not offered: device groups, RGL materials, plugin properties, an update that changes dims, layout or channel count. */
+ * The measured values of an RGB RGL material: mrl_material_update_rgl_values of merl_hip_fit_rgl.h (this call refuses the kind).
+ * Not offered: device groups, spectral RGL materials, plugin properties, an update that changes dims, layout or channel count. */
 int mrl_material_update_table(mrl_ctx *ctx, int id, const double *planar, int flags);
 
 /* ---- GGX conductors ----

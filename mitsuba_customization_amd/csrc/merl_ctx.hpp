@@ -22,6 +22,8 @@
 //   merl_table_dir_grad.hip  the same on RGB tables (mrl_table_grad_dir_batch / _queue)
 //   merl_nch_dir_grad.hip  the same on n-channel tables (mrl_table_grad_dir_batch_nch / _queue_nch)
 //   merl_rgl_dir_grad.hip  the same on RGB RGL materials (mrl_rgl_grad_dir_batch / _queue)
+//   merl_rgl_values_grad.hip  the adjoint of eval in the measured values of RGB RGL materials and their update in place
+//                          (include/merl_hip_fit_rgl.h): scatter, fold and write kernels + calls
 #pragma once
 #include "../../include/merl_hip.h"
 
@@ -130,7 +132,8 @@ struct mrl_ctx {
     //   BUF_QUEUES       kind-partitioned mixed batches: [2][n] unit indices + partition work area behind them
     //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
     //   BUF_GRAD_BRICKS  the table-gradient calls: gradient bricks, one 256-B record per cell of every table of a call (merl_table_grad.hip),
-    //                    per cell and channel group of 4 for n-channel tables (merl_table_grad_nch.hip)
+    //                    per cell and channel group of 4 for n-channel tables (merl_table_grad_nch.hip), one 128 / 256 / 512-B record per
+    //                    (bracket, cell) of every RGL target (merl_rgl_values_grad.hip)
     //   BUF_GGX_GRAD     mrl_ggx_grad_batch: one 256-B row of partial sums per block + the sums of a host-array call (merl_ggx_grad.hip)
     //   BUF_GGX_GRAD_MAT mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue: one 256-B row per block and target + the sums of a host-array
     //                    call (merl_ggx_grad_mat.hip); its own buffer, so that what a captured graph points at never moves

@@ -49,15 +49,21 @@ def _any_backward(gpu, wi, wo, grad_rgb, mat=None, material=0, want=("wi", "wo")
     return tuple(sum(side[1:], side[0]) for side in zip(*parts))
 
 
-def _holds_rgl(gpu):
-    """does the context hold a live RGB RGL material?  (a released slot has no info: MerlHipError)"""
+def _rgl_ids(gpu):
+    """the ids of the context's live RGB RGL materials, ascending  (a released slot has no info: MerlHipError)"""
+    ids = []
     for mid in range(gpu.material_count()):
         try:
             if gpu.material_info(mid)[0] == host.KIND_RGL:
-                return True
+                ids.append(mid)
         except host.MerlHipError:
             pass
-    return False
+    return ids
+
+
+def _holds_rgl(gpu):
+    """does the context hold a live RGB RGL material?"""
+    return bool(_rgl_ids(gpu))
 
 
 class _Eval(torch.autograd.Function):
@@ -112,14 +118,24 @@ class _SpectralEval(torch.autograd.Function):
 
 
 class _Materials:
-    """The tensors behind the materials of one differentiable call: entries (kind "table" / "ggx", material id, tensor).
+    """The tensors behind the materials of one differentiable call: entries (kind "table" / "ggx" / "rgl", material id, tensor).
     refresh() makes every material hold its tensor's current values; gradients() is _Eval's material_call."""
 
-    def __init__(self, gpu, mat, material, tables, params, n_channels=None):
+    def __init__(self, gpu, mat, material, tables, params, n_channels=None, values=None):
         self.gpu, self.mat, self.material, self.n_channels = gpu, mat, material, n_channels
         as_dict = lambda v: {} if v is None else ({int(k): t for k, t in v.items()} if isinstance(v, dict) else {int(material): v})
-        self.entries = [("table", k, t) for k, t in as_dict(tables).items()] + [("ggx", k, t) for k, t in as_dict(params).items()]
+        if isinstance(values, (list, tuple)):                   # one tensor per live RGB RGL material of the context, in the order of their ids
+            ids = _rgl_ids(gpu)
+            if len(ids) != len(values):
+                raise ValueError(f"values=: {len(values)} tensors for the context's {len(ids)} RGB RGL materials (or pass {{id: tensor}})")
+            values = dict(zip(ids, values))
+        self.entries = [("table", k, t) for k, t in as_dict(tables).items()] + [("ggx", k, t) for k, t in as_dict(params).items()] + \
+                       [("rgl", k, t) for k, t in as_dict(values).items()]
         for kind, _, t in self.entries:
+            if kind == "rgl":
+                if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.float64):
+                    raise ValueError("values=: torch.float32 or torch.float64 tensors [n_phi, n_theta, 3, ny, nx]")
+                continue
             if not torch.is_tensor(t) or t.dtype != torch.float64:
                 raise ValueError("tables= / params=: torch.float64 tensors")
             if kind == "ggx" and tuple(t.shape) != (7,):
@@ -140,6 +156,8 @@ class _Materials:
                 continue
             if kind == "table":
                 self.gpu.update_table(mid, t.detach(), keep_sampling=True)
+            elif kind == "rgl":                                 # the image holds Floats: an f64 tensor is rounded once, on the device
+                self.gpu.update_rgl_values(mid, t.detach().to(torch.float32).contiguous())
             else:
                 p = t.detach().cpu().tolist()                   # 7 values to the host: waits for whatever computes them
                 self.gpu.update_ggx(mid, p[0], p[1:4], p[4:7])
@@ -159,6 +177,11 @@ class _Materials:
                 grads = gpu.table_grad_mat(wi, wo, g, ids, mat=self.mat, material=self.material)
             for i, grad in zip(tables, grads):
                 out[i] = grad
+        rgl = [i for i in needed if self.entries[i][0] == "rgl"]
+        if rgl:                                                 # one launch for all targets, split by rgl_values_grad_layout
+            grads = gpu.rgl_values_grad(wi, wo, g, [self.entries[i][1] for i in rgl], mat=self.mat, material=self.material)
+            for i, grad in zip(rgl, grads):
+                out[i] = grad.to(self.entries[i][2].dtype)
         if ggx:
             ids = [self.entries[i][1] for i in ggx]
             if self.mat is None and ids == [self.material]:
@@ -170,10 +193,10 @@ class _Materials:
         return out
 
 
-def _apply(gpu, wi, wo, forward_call, backward_call, mat, material, tables=None, params=None, n_channels=None):
-    if tables is None and params is None:
+def _apply(gpu, wi, wo, forward_call, backward_call, mat, material, tables=None, params=None, n_channels=None, values=None):
+    if tables is None and params is None and values is None:
         return _Eval.apply(wi, wo, forward_call, backward_call, None)
-    m = _Materials(gpu, mat, material, tables, params, n_channels)
+    m = _Materials(gpu, mat, material, tables, params, n_channels, values)
     m.refresh()
     return _Eval.apply(wi, wo, forward_call, backward_call, m.gradients, *m.values)
 
@@ -207,13 +230,19 @@ def table_eval(ctx, wi, wo, mat=None, material: int = 0, tables=None):
                   mat, material, tables=tables)
 
 
-def rgl_eval(ctx, wi, wo, mat=None, material: int = 0):
+def rgl_eval(ctx, wi, wo, mat=None, material: int = 0, values=None):
     """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be RGB RGL materials
     (upload_rgl / load_rgl): the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose
     id names no live RGB RGL material receives a zero gradient.  The gradient is the exact one of the piecewise function in the cells
-    eval selects (include/merl_hip_diff_rgl.h): piecewise smooth, like the function.  The file's values are not differentiable."""
+    eval selects (include/merl_hip_diff_rgl.h): piecewise smooth, like the function.
+    values=: a device tensor [n_phi, n_theta, 3, ny, nx] (f32 or f64) for the single material, {id: tensor} with mat=, or a list with
+    one tensor per live RGB RGL material of the context in the order of their ids: the call is differentiable in the files' measured
+    values too (include/merl_hip_fit_rgl.h).  Forward writes a tensor into its resident material with
+    MerlHip.update_rgl_values — in place, from device memory, rounded to float — only when (data_ptr, _version) differs from what that
+    material last received; backward is one MerlHip.rgl_values_grad launch for all tensors that need a gradient, cast to each tensor's
+    dtype.  vndf, ndf, sigma, luminance and the grids are not differentiable."""
     return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(ctx.rgl_grad_dir, mat=mat, material=material),
-                  mat, material)
+                  mat, material, values=values)
 
 
 def rgl_spectral_eval(ctx, wi, wo, wavelengths, mat=None, material: int = 0):
@@ -233,15 +262,16 @@ def rgl_spectral_eval(ctx, wi, wo, wavelengths, mat=None, material: int = 0):
     return _SpectralEval.apply(wi, wo, wavelengths, forward, partial(ctx.rgl_grad_dir_spectral, mat=mat, material=material))
 
 
-def eval(ctx, wi, wo, mat=None, material: int = 0, tables=None, params=None):
+def eval(ctx, wi, wo, mat=None, material: int = 0, tables=None, params=None, values=None):
     """MerlHip.eval(wi, wo, mat, material), differentiable in wi and wo, for GGX conductors, RGB tables, RGB RGL materials and batches
     that mix them.  Single material: the backward pass is the gradient call of that material's kind.  With mat=: the sum of
     table_grad_dir and ggx_grad_dir — and of rgl_grad_dir when the context holds a live RGB RGL material —, each exactly zero on the
     others' units; units of kinds this RGB-wide call does not serve (n-channel tables, spectral RGL materials — their values are
     [n, W]: rgl_spectral_eval() is their differentiable eval —, released or unknown ids) receive zeros.
-    tables= / params=: as in table_eval() and ggx_eval(), for the tables and the conductors of a mixed batch."""
+    tables= / params= / values=: as in table_eval(), ggx_eval() and rgl_eval(), for the tables, the conductors and the RGL files of a
+    mixed batch."""
     return _apply(ctx, wi, wo, partial(ctx.eval, mat=mat, material=material), partial(_any_backward, ctx, mat=mat, material=material),
-                  mat, material, tables=tables, params=params)
+                  mat, material, tables=tables, params=params, values=values)
 
 
 def table_eval_nch(ctx, wi, wo, n_channels: int, mat=None, material: int = 0, tables=None):

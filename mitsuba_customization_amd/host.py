@@ -89,6 +89,10 @@ GGX_GRAD_MAX_TARGETS = 16           # MRL_GGX_GRAD_MAX_TARGETS
 # every symbol include/merl_hip_update.h declares: new values for a resident material in place, and the row marginal's read-back
 UPDATE_ABI_SYMBOLS = ("mrl_material_update_table", "mrl_material_update_ggx", "mrl_material_sampling")
 UPDATE_KEEP_SAMPLING = 1            # MRL_UPDATE_KEEP_SAMPLING
+# every symbol include/merl_hip_fit_rgl.h declares: the adjoint of eval in the values of RGB RGL materials, and their update in place
+FIT_RGL_ABI_SYMBOLS = ("mrl_rgl_values_grad_batch", "mrl_rgl_values_grad_queue", "mrl_rgl_values_shape", "mrl_rgl_values_grad_layout",
+                       "mrl_material_update_rgl_values")
+RGL_GRAD_MAX_TARGETS = 16           # MRL_RGL_GRAD_MAX_TARGETS
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -254,6 +258,11 @@ _CALLS["queue", "ggx_grad_mat"] = ("mrl_ggx_grad_queue", _FAMILIES["queue"][1] +
 _CALLS["material", "update_table"] = ("mrl_material_update_table", ("id", "planar", "flags"), (), ())
 _CALLS["material", "update_ggx"] = ("mrl_material_update_ggx", ("id", "alpha", "eta", "k"), (), ())
 _CALLS["material", "sampling"] = ("mrl_material_sampling", ("id", "out", "max_doubles"), (), ())
+# the adjoint of eval in the values of RGB RGL materials and their update in place (include/merl_hip_fit_rgl.h): the table adjoint's rows
+_RGL_TARGETS = ("target_ids", "n_targets", "grad_values")
+_CALLS["batch", "rgl_values_grad"] = ("mrl_rgl_values_grad_batch", _FAMILIES["batch"][1] + _RGL_TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
+_CALLS["queue", "rgl_values_grad"] = ("mrl_rgl_values_grad_queue", _FAMILIES["queue"][1] + _RGL_TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
+_CALLS["material", "update_rgl_values"] = ("mrl_material_update_rgl_values", ("id", "rgb", "flags"), (), ())
 
 
 _lib = None
@@ -308,6 +317,8 @@ def load_library(path: Optional[str] = None):
     L.mrl_table_grad_batch.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_size_t, vp]
     L.mrl_table_grad_layout.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_size_t)]
     L.mrl_table_grad_layout_nch.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    L.mrl_rgl_values_shape.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.mrl_rgl_values_grad_layout.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_size_t)]
     L.mrl_ggx_grad_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int32, C.c_size_t, vp, vp]
     L.mrl_ggx_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
@@ -502,6 +513,21 @@ def table_grad_layout(dims_list) -> list:
     if load_library().mrl_table_grad_layout(flat, len(dims_list), offsets) != 0:
         raise ValueError(f"table_grad_layout: 1..{TABLE_GRAD_MAX_TARGETS} targets of at most 2^31 - 1 cells in all, every dim >= 1")
     return [int(v) for v in offsets[:len(dims_list) + 1]]
+
+
+def rgl_values_grad_layout(shapes) -> list:
+    """mrl_rgl_values_grad_layout: where each target's slice of the rgl_values_grad / rgl_values_grad_queue buffer starts, in f64
+    values; shapes: (n_phi, n_theta, 3, ny, nx) per target, as MerlHip.rgl_values_shape() reports them.  Returns n_targets + 1 offsets,
+    the last one the buffer's size.  ValueError for what the calls refuse (include/merl_hip_fit_rgl.h)."""
+    shapes = [tuple(sh) for sh in shapes]
+    if any(len(sh) != 5 or any(not -2**31 <= int(d) < 2**31 for d in sh) for sh in shapes):
+        raise ValueError("rgl_values_grad_layout: every target has five dims that fit an int")
+    flat = (C.c_int * (5 * len(shapes)))(*[int(d) for sh in shapes for d in sh])
+    offsets = (C.c_size_t * (len(shapes) + 1))()
+    if load_library().mrl_rgl_values_grad_layout(flat, len(shapes), offsets) != 0:
+        raise ValueError(f"rgl_values_grad_layout: 1..{RGL_GRAD_MAX_TARGETS} targets of shape (n_phi >= 1, n_theta >= 1, 3, ny >= 2, nx >= 2) "
+                         "and at most 2^31 - 1 workspace records in all")
+    return list(offsets)
 
 
 def table_grad_layout_nch(dims_list, n_channels: int) -> list:
@@ -775,6 +801,28 @@ class MerlHip:
         self._forget_resident(mid)
         _material_call(self, "update_ggx", id=int(mid), alpha=alpha, eta=(C.c_float * 3)(*eta), k=(C.c_float * 3)(*k))
 
+    def rgl_values_shape(self, mid: int) -> tuple:
+        """(n_phi, n_theta, 3, ny, nx) of the rgb array of the RGB RGL material `mid` (mrl_rgl_values_shape)."""
+        shape = (C.c_int * 5)()
+        self._check(self._lib.mrl_rgl_values_shape(self._ctx, int(mid), shape), "mrl_rgl_values_shape")
+        return tuple(int(d) for d in shape)
+
+    def update_rgl_values(self, mid: int, rgb):
+        """New measured values for the resident RGB RGL material `mid` (mrl_material_update_rgl_values): same id, same addresses;
+        vndf, ndf, sigma, luminance and the grids stay as they are (pdf and sampled directions keep their bits).  rgb: f32, contiguous,
+        [n_phi, n_theta, 3, ny, nx] as uploaded — a numpy array (checked for non-finite values, staged) or a device tensor (read in
+        place on torch's current stream: no copy, no synchronisation; finite values are the caller's responsibility).  ValueError for
+        a wrong dtype, layout or shape."""
+        shape = self.rgl_values_shape(mid)
+        if _is_tensor(rgb) and not rgb.is_cuda:
+            raise ValueError("rgb: torch tensors must live on the GPU (pass a numpy array for host data)")
+        if tuple(rgb.shape) != shape:
+            raise ValueError(f"rgb: shape {tuple(rgb.shape)}, the material was uploaded from {shape}")
+        ptr = _addr(rgb, np.float32, None, None, "rgb")
+        self._prep(rgb)
+        self._forget_resident(mid)
+        _material_call(self, "update_rgl_values", id=int(mid), rgb=ptr, flags=0)
+
     def _forget_resident(self, mid: int):
         """diff.py records on this object which tensor a material last received (tables= / params=); whoever changes or releases the
         material drops that record"""
@@ -955,6 +1003,47 @@ class MerlHip:
         not among the targets.  Returns a tuple of f64 arrays [3, *dims_k], views of one buffer that holds the targets end to end;
         numpy in -> numpy out, device tensors in -> device tensors out; out= (that one buffer, any shape) is accumulated into."""
         return self._table_grad_targets("batch", wi, wo, grad_rgb, targets, mat, material, out)
+
+    def _rgl_values_grad(self, family, wi, wo, grad_rgb, targets, mat, material, out, queue=(None, None, None)):
+        """One call of include/merl_hip_fit_rgl.h through its row of _CALLS: _table_grad_targets for RGL targets.  Returns the targets'
+        gradients [n_phi, n_theta, 3, ny, nx] as views of one f64 buffer that holds them end to end, in the order of `targets`."""
+        targets = [int(t) for t in targets]
+        symbol = _CALLS[family, "rgl_values_grad"][0]
+        if not 1 <= len(targets) <= RGL_GRAD_MAX_TARGETS:
+            raise MerlHipError(ERR_INVALID, symbol, f"1..{RGL_GRAD_MAX_TARGETS} targets")
+        shapes = [self.rgl_values_shape(t) for t in targets]        # ERR_MATERIAL for a target that is no live RGB RGL material
+        offsets = rgl_values_grad_layout(shapes)
+        total = offsets[-1]
+        if _is_tensor(wi):
+            import torch
+            if out is None:
+                out = torch.zeros((total,), dtype=torch.float64, device=wi.device)
+            if not _is_tensor(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != total:
+                raise ValueError(f"out: need a contiguous torch.float64 tensor of {total} values (the targets end to end)")
+            ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.zeros((total,), dtype=np.float64)
+            if not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.size != total:
+                raise ValueError(f"out: need a C-contiguous numpy float64 array of {total} values (the targets end to end)")
+            ptr = out.ctypes.data
+        more = {"target_ids": (C.c_int32 * len(targets))(*targets), "n_targets": len(targets), "grad_values": ptr}
+        _stream_call(self, family, "rgl_values_grad", (wi, wo, grad_rgb), None, 3, None, mat, material, *queue, more=more)
+        flat = out.reshape(-1)
+        return tuple(flat[a:b].reshape(sh) for a, b, sh in zip(offsets, offsets[1:], shapes))
+
+    def rgl_values_grad(self, wi, wo, grad_rgb, targets, mat=None, material: int = 0, out=None):
+        """G_k += (d eval / d R_k)^T grad_rgb for every RGB RGL material in `targets` in one launch (mrl_rgl_values_grad_batch,
+        include/merl_hip_fit_rgl.h): the adjoint of eval in a file's measured values.  A unit adds into the target its material id
+        names — mat[i], or `material` for all units — and into nothing if that id is not among the targets.  Returns a tuple of f64
+        arrays [n_phi, n_theta, 3, ny, nx], views of one buffer that holds the targets end to end; numpy in -> numpy out, device
+        tensors in -> device tensors out; out= (that one buffer, any shape) is accumulated into."""
+        return self._rgl_values_grad("batch", wi, wo, grad_rgb, targets, mat, material, out)
+
+    def rgl_values_grad_queue(self, wi, wo, grad_rgb, queue, count, targets, mat=None, material: int = 0, capacity=None, out=None):
+        """rgl_values_grad() of the slots queue[0 .. min(count, capacity)) (mrl_rgl_values_grad_queue); a slot listed twice adds twice.
+        GPU tensors only."""
+        return self._rgl_values_grad("queue", wi, wo, grad_rgb, targets, mat, material, out, queue=(queue, count, capacity))
 
     def ggx_grad(self, wi, wo, grad_rgb, material: int, curvature=None, normal: bool = False, out=None):
         """The parameter gradient of eval on a GGX material (mrl_ggx_grad_batch), parameters in the order (alpha, eta[3], k[3]):

@@ -1,0 +1,120 @@
+// rgl_values_grad_host_harness.hip — the per-lane function the kernels of csrc/merl_rgl_values_grad.hip run
+// (csrc/merl_rgl_values_grad.hpp: rgl::values_grad_unit, values_slot_term, fold_sources, values_texel) and the product's image builder
+// (csrc/merl_rgl.hip) compiled for the HOST, so that tests/test_rgl_values_grad_cpu.py can hold the gradient of eval in an RGL
+// material's values to its reference in a container without a GPU, and run the same code under the host sanitizers.  No HIP runtime
+// call is made.  Built by the test with hipcc.  Modelled on tests/rgl_dir_grad_host_harness.hip.
+//   usage: rgl_values_grad_host_harness grad <fields.bin> <units.bin> <out.bin>
+//     fields.bin: as tests/rgl_dir_grad_host_harness.hip reads it
+//     units.bin:  uint64 n, then wi[n][3] wo[n][3] g[n][3] (float32), then one float64: what the two arrays hold before anything is added
+//     out.bin:    float64 [2][n_phi][n_theta][3][ny][nx]: the units through the gradient bricks and the fold; through values_texel
+//   usage: rgl_values_grad_host_harness fold <n_phi> <n_theta> <nx> <ny> <out.bin>
+//     the fold alone, in passes of 50 slots: in pass p workspace double 50 p + e holds 2^e (a padding slot too), every other 0
+//     out.bin:    float64 [passes][n_phi][n_theta][3][ny][nx]
+#include "../mitsuba_customization_amd/csrc/merl_rgl.hip"
+#include "../mitsuba_customization_amd/csrc/merl_rgl_values_grad.hpp"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+namespace {
+
+// k_rgl_values_fold's body
+void fold(const std::vector<double> &bricks, double *planar, int n_phi, int n_theta, int nx, int ny)
+{
+    size_t t = 0;
+    for (int ip = 0; ip < n_phi; ++ip)
+        for (int it = 0; it < n_theta; ++it)
+            for (int c = 0; c < 3; ++c)
+                for (int y = 0; y < ny; ++y)
+                    for (int x = 0; x < nx; ++x, ++t) {
+                        size_t src[16];
+                        const int n = mrl::rgl::fold_sources(n_phi, n_theta, nx, ny, ip, it, c, y, x, src);
+                        double acc = 0.0;
+                        for (int k = 0; k < n; ++k) acc += bricks.at(src[k]);
+                        if (acc != 0.0) planar[t] += acc;
+                    }
+}
+
+int write_doubles(const char *path, const std::vector<double> &v)
+{
+    FILE *f = std::fopen(path, "wb");
+    if (!f || std::fwrite(v.data(), 8, v.size(), f) != v.size()) return 5;
+    std::fclose(f);
+    return 0;
+}
+
+int run_fold(int argc, char **argv)
+{
+    if (argc < 7) return 2;
+    const int n_phi = std::atoi(argv[2]), n_theta = std::atoi(argv[3]), nx = std::atoi(argv[4]), ny = std::atoi(argv[5]);
+    const int S = (n_phi > 1 ? 2 : 1) * (n_theta > 1 ? 2 : 1);
+    const size_t doubles = mrl::rgl::values_records(n_phi, n_theta, nx, ny) * (size_t)(16 * S);
+    const size_t texels = (size_t)n_phi * n_theta * 3 * ny * nx, passes = (doubles + 49) / 50;
+    std::vector<double> out(passes * texels, 0.0);
+    for (size_t p = 0; p < passes; ++p) {
+        std::vector<double> bricks(doubles, 0.0);
+        for (size_t e = 0; e < 50 && 50 * p + e < doubles; ++e) bricks[50 * p + e] = std::ldexp(1.0, (int)e);
+        fold(bricks, out.data() + p * texels, n_phi, n_theta, nx, ny);
+    }
+    return write_doubles(argv[6], out);
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc >= 2 && !std::strcmp(argv[1], "fold")) return run_fold(argc, argv);
+    if (argc < 5 || std::strcmp(argv[1], "grad")) return 2;
+    FILE *f = std::fopen(argv[2], "rb");
+    if (!f) return 3;
+    int h[9];
+    if (std::fread(h, 4, 9, f) != 9) return 3;
+    mrl::RglFields F;
+    F.n_phi = h[0]; F.n_theta = h[1]; F.res[0] = h[2]; F.res[1] = h[3]; F.res_ndf[0] = h[4]; F.res_ndf[1] = h[5]; F.res_sigma[0] = h[6]; F.res_sigma[1] = h[7];
+    F.jacobian = h[8]; F.n_wl = 0; F.wavelengths = nullptr;
+    if (mrl::rgl_check_shapes(F)) return 3;
+    std::vector<std::vector<float>> keep;
+    bool ok = true;
+    auto rd = [&](size_t n) { keep.emplace_back(n); ok = ok && std::fread(keep.back().data(), 4, n, f) == n; return keep.back().data(); };
+    const size_t per = (size_t)F.res[0] * F.res[1], sl = (size_t)F.n_phi * F.n_theta;
+    F.phi_i = rd(F.n_phi); F.theta_i = rd(F.n_theta); F.ndf = rd((size_t)F.res_ndf[0] * F.res_ndf[1]); F.sigma = rd((size_t)F.res_sigma[0] * F.res_sigma[1]);
+    F.vndf = rd(sl * per); F.luminance = rd(sl * per); F.rgb = rd(sl * per * 3);
+    std::fclose(f);
+    if (!ok) return 3;
+    if (const char *why = mrl::rgl_check_fields(F)) { std::fprintf(stderr, "%s\n", why); return 4; }
+    std::vector<float> blob;
+    const mrl::RglLayout L = mrl::rgl_build_image(F, blob);
+    const mrl::RglDev r = mrl::rgl_descriptor(F, L, blob.data());
+    f = std::fopen(argv[3], "rb");
+    if (!f) return 3;
+    unsigned long long n = 0;
+    if (std::fread(&n, 8, 1, f) != 1) return 3;
+    std::vector<float> wi(3 * n), wo(3 * n), g(3 * n);
+    double start = 0.0;
+    if (std::fread(wi.data(), 4, 3 * n, f) != 3 * n || std::fread(wo.data(), 4, 3 * n, f) != 3 * n || std::fread(g.data(), 4, 3 * n, f) != 3 * n ||
+        std::fread(&start, 8, 1, f) != 1) return 3;
+    std::fclose(f);
+    const mrl::rgl::GridMem grids{ r.phi, r.theta, r.wavelengths };
+    const int S = r.slices();
+    const size_t texels = sl * per * 3;
+    std::vector<double> bricks(mrl::rgl::values_records(r.n_phi, r.n_theta, r.nx, r.ny) * (size_t)(16 * S), 0.0), out(2 * texels, start);
+    size_t live = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const mrl::rgl::ValuesGradUnit u = mrl::rgl::values_grad_unit(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], &g[3 * i]);
+        if (!u.live) continue;
+        ++live;
+        for (int slot = 0; slot < 12 * S; ++slot)
+            bricks.at((size_t)u.record * (size_t)(16 * S) + (size_t)slot) += mrl::rgl::values_slot_term(u.a, u.ws, u.wc, S, slot);
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < S; ++k)
+                for (int j = 0; j < 4; ++j) {
+                    const double v = u.a[c] * u.ws[k] * u.wc[j];
+                    if (v != 0.0) out.at(texels + mrl::rgl::values_texel(r, u, c, k, j)) += v;
+                }
+    }
+    fold(bricks, out.data(), r.n_phi, r.n_theta, r.nx, r.ny);
+    if (const int rc = write_doubles(argv[4], out)) return rc;
+    std::printf("rgl values-gradient host harness ok: %llu units, %zu live\n", n, live);
+    return 0;
+}

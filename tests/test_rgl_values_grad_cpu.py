@@ -1,0 +1,161 @@
+"""The gradient of eval in the values of RGB RGL materials (include/merl_hip_fit_rgl.h) without a GPU: the header
+against the library's symbols, the layout function, the per-lane function and the fold compiled for the host (and once more under
+the host sanitizers) against the autograd reference of tests/rgl_values_grad_reference.py, the fold's record -> texel map, and the
+compiled kernels' assembly.
+
+Measured worst |G - R| / S per file, host-compiled per-lane function + fold and plain form alike (the bar is 1e-6):
+iso 2.2e-9, iso_nojac 4.9e-9, iso_theta1 6.5e-10, iso_phi2 1.6e-9, aniso 1.1e-8, aniso_red2 1.0e-9, aniso_red4 4.6e-9,
+aniso_uneven 5.8e-10, iso_rows 9.5e-11, iso_cols 3.7e-10, iso_negative 1.9e-9, ggx_res32 5.6e-8 — what eval's own f64 building
+blocks (v_rcp / v_rsq seeds with one Newton step, the atan polynomial) leave in the cell fractions next to torch's libm."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import rgl_values_grad_reference as vref
+
+ROOT = vref.ROOT
+
+
+def test_header_declares_and_library_exports_the_rgl_values_calls():
+    import ctypes as C
+    from mitsuba_customization_amd import build, host
+    text = open(os.path.join(ROOT, "include", "merl_hip_fit_rgl.h")).read()
+    assert re.search(r'#include\s+"merl_hip.h"', text)
+    assert re.search(r"#define\s+MRL_RGL_GRAD_MAX_TARGETS\s+16\b", text) and host.RGL_GRAD_MAX_TARGETS == 16
+    code = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    protos = dict(re.findall(r"^[ \t]*int[ \t]+(mrl_\w+)[ \t]*\(([^()]*)\)[ \t]*;", code, flags=re.M))
+    assert set(protos) == set(host.FIT_RGL_ABI_SYMBOLS) and len(host.FIT_RGL_ABI_SYMBOLS) == 5
+    others = (host.ABI_SYMBOLS, host.FIT_ABI_SYMBOLS, host.DIFF_ABI_SYMBOLS, host.DIFF_TABLE_ABI_SYMBOLS, host.DIFF_NCH_ABI_SYMBOLS,
+              host.DIFF_RGL_ABI_SYMBOLS, host.FIT_TABLE_ABI_SYMBOLS, host.FIT_NCH_ABI_SYMBOLS, host.FIT_GGX_ABI_SYMBOLS, host.UPDATE_ABI_SYMBOLS)
+    assert not set(host.FIT_RGL_ABI_SYMBOLS) & set().union(*map(set, others))
+    for word in ("NOT touched", "Out of scope", "luminance distribution is NOT rebuilt", "caller's responsibility", "POINTERS", "keeps its bits"):
+        assert word in text, word
+    build.build_lib()
+    lib = host.load_library()
+
+    def c_class(decl):
+        if "*" in decl or "[" in decl:
+            return "pointer"
+        return {"int": "i32", "int32_t": "i32", "size_t": "u64"}[[w for w in re.findall(r"\w+", decl) if w != "const"][0]]
+
+    def ctypes_class(t):
+        if t in (C.c_int, C.c_int32):
+            return "i32"
+        if t is C.c_size_t:
+            return "u64"
+        return "pointer"
+    for name in host.FIT_RGL_ABI_SYMBOLS:
+        assert hasattr(lib, name), name
+        assert [ctypes_class(t) for t in getattr(lib, name).argtypes] == [c_class(p) for p in protos[name].split(",")], name
+    t = (C.c_int32 * 1)(0)
+    assert lib.mrl_rgl_values_grad_batch(None, None, None, None, None, 0, 4, t, 1, None) == -1               # no context: MRL_ERR_INVALID
+    assert lib.mrl_rgl_values_grad_queue(None, None, None, None, None, 0, None, None, 4, t, 1, None) == -1
+    assert lib.mrl_rgl_values_shape(None, 0, (C.c_int * 5)()) == -1
+    assert lib.mrl_material_update_rgl_values(None, 0, None, 0) == -1
+
+
+def test_layout_function_on_hand_computed_shapes_and_its_refusals():
+    from mitsuba_customization_amd import host
+    L = host.rgl_values_grad_layout
+    # doubles of [n_phi][n_theta][3][ny][nx], end to end
+    assert L([(1, 6, 3, 12, 12)]) == [0, 2592]
+    assert L([(1, 6, 3, 12, 12), (8, 4, 3, 10, 12), (1, 1, 3, 2, 2)]) == [0, 2592, 2592 + 11520, 2592 + 11520 + 12]
+    assert L([(2, 3, 3, 5, 4)] * 16)[-1] == 16 * 360
+    for bad in ([], [(1, 6, 3, 12, 12)] * 17, [(0, 6, 3, 12, 12)], [(1, 0, 3, 12, 12)], [(1, 6, 4, 12, 12)], [(1, 6, 3, 1, 12)], [(1, 6, 3, 12, 1)],
+                [(1, 6, 3, 12)], [(1, 6, 3, 12, 2 ** 31)]):
+        with pytest.raises(ValueError):
+            L(bad)
+    # records: (n_phi - 1 or 1) (n_theta - 1 or 1) (ny - 1) (nx - 1) per target, at most 2^31 - 1 = 2,147,483,647 over all targets
+    assert L([(1, 2, 3, 46341, 46341)])[-1] == 2 * 3 * 46341 * 46341                  # 46340^2 = 2,147,395,600 records: fits
+    with pytest.raises(ValueError):
+        L([(1, 3, 3, 46341, 46341)])                                                   # two brackets of 46340^2 records
+    assert len(L([(1, 2, 3, 46341, 46341), (1, 1, 3, 297, 297)])) == 3                 # + 296^2 = 87,616: 2,147,483,216
+    with pytest.raises(ValueError):
+        L([(1, 2, 3, 46341, 46341), (1, 1, 3, 298, 298)])                              # + 297^2 = 88,209: 2,147,483,809
+    lib = host.load_library()
+    assert lib.mrl_rgl_values_grad_layout(None, 1, None) == -1
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    return vref.build_harness(tmp_path_factory)
+
+
+@pytest.mark.parametrize("name", vref.FILE_NAMES)
+def test_per_lane_function_and_fold_against_the_reference(harness, tmp_path, name):
+    c = vref.case(name)
+    start = -0.0                                                   # x + 0 would turn it into +0: an unreached texel keeps its bits
+    G_bricks, G_plain = vref.run_harness(harness, tmp_path, c["fields"], c["wi"], c["wo"], c["g"], start)
+    vref.check(G_bricks, c, start, f"{name} host bricks + fold")
+    vref.check(G_plain, c, start, f"{name} host plain")
+    if name == "iso_negative":                                     # the clamp is at work: some channel of some unit contributes nothing
+        d = vref.values_grad(c["arrays"], c["wi"][c["alive"]], c["wo"][c["alive"]], c["g"][c["alive"]], rgb=np.abs(np.asarray(c["fields"]["rgb"])))
+        assert np.abs(d[1] - c["S"]).max() > 0.0
+
+
+@pytest.mark.parametrize("name", ["iso", "aniso"])
+def test_per_lane_function_and_fold_under_the_host_sanitizers(tmp_path_factory, tmp_path, name):
+    san = vref.build_harness(tmp_path_factory, sanitize=True)
+    c = vref.case(name)
+    G_bricks, G_plain = vref.run_harness(san, tmp_path, c["fields"], c["wi"], c["wo"], c["g"], 0.0)
+    vref.check(G_bricks, c, 0.0, f"{name} host bricks + fold, ASan + UBSan")
+    vref.check(G_plain, c, 0.0, f"{name} host plain, ASan + UBSan")
+
+
+@pytest.mark.parametrize("n_phi", [1, 2, 3])
+@pytest.mark.parametrize("n_theta", [1, 2, 3])
+def test_fold_maps_every_slot_to_the_texel_the_copy_rule_implies(harness, tmp_path, n_phi, n_theta):
+    nx, ny = 3, 4
+    S = (2 if n_phi > 1 else 1) * (2 if n_theta > 1 else 1)
+    records = max(n_phi - 1, 1) * max(n_theta - 1, 1) * (nx - 1) * (ny - 1)
+    doubles = records * 16 * S
+    passes = (doubles + 49) // 50
+    out = tmp_path / "fold.bin"
+    r = subprocess.run([str(harness), "fold", str(n_phi), str(n_theta), str(nx), str(ny), str(out)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = np.fromfile(out, np.float64).reshape(passes, n_phi, n_theta, 3, ny, nx)
+    seen = 0
+    for p in range(passes):
+        # every slot a distinct power of two within its pass (sums of at most 16 of 50 distinct powers are exact); padding slots hold
+        # one too, and no texel may pick it up
+        want = vref.fold_expected(n_phi, n_theta, nx, ny, lambda at: 2.0 ** (at - 50 * p) if 50 * p <= at < 50 * p + 50 else 0.0)
+        assert np.array_equal(got[p], want), (n_phi, n_theta, p)
+        seen += sum(bin(int(v)).count("1") for v in want.reshape(-1))
+    assert seen == records * 12 * S                                # every used slot reaches exactly one texel
+
+
+def _kernels(asm):
+    """{demangled kernel name: (scratch bytes per lane, VGPRs, kernel text)}"""
+    blocks = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S)
+    names = subprocess.run(["c++filt"] + [b[0] for b in blocks], capture_output=True, text=True).stdout.splitlines()
+    out = {}
+    for (mangled, body), d in zip(blocks, names):
+        m = re.search(r"^%s:(.*?)\.end_amdhsa_kernel" % re.escape(mangled), asm, re.S | re.M)
+        short = re.sub(r"^(void )?mrl::\(anonymous namespace\)::", "", d).split("(")[0]
+        out[short] = (int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)),
+                      int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)), m.group(1) if m else "")
+    return out
+
+
+def test_compiled_kernels_add_with_f64_atomics_and_keep_their_registers(tmp_path):
+    asm_path = tmp_path / "vg.s"
+    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(asm_path), vref.KERNEL_SOURCE],
+                          timeout=900)
+    asm = open(asm_path).read()
+    kernels = _kernels(asm)
+    assert "global_atomic_add_f64" in asm
+    assert "cmpswap" not in asm
+    accumulate = [k for k in kernels if k.startswith(("k_rgl_values_bricks<", "k_rgl_values_plain<"))]
+    # 2 (ids / one material's four shapes) x 2 (whole arrays / queue): 10 brick kernels, 4 plain ones
+    assert len(accumulate) == 14 and {"k_rgl_values_fold", "k_rgl_values_write"} <= set(kernels)
+    for name, (scratch, vgprs, text) in kernels.items():
+        print(f"{name}: {vgprs} VGPRs, {scratch} B scratch")
+        assert scratch == 0, (name, scratch)
+    for name in accumulate:
+        atomics = set(re.findall(r"\b((?:global|flat|buffer)_atomic_\w+)", kernels[name][2]))
+        assert atomics == {"global_atomic_add_f64"}, (name, atomics)
+    for name in ("k_rgl_values_fold", "k_rgl_values_write"):
+        assert not re.search(r"_atomic_", kernels[name][2])
