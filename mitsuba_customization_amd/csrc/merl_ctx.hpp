@@ -11,6 +11,9 @@
 //                          tables: mrl_table_grad_batch_mat / mrl_table_grad_queue of merl_hip_fit_table.h): scatter kernels + calls
 //   merl_table_grad_nch.hip  the same adjoint on n-channel tables (mrl_table_grad_batch_nch / mrl_table_grad_queue_nch of
 //                          merl_hip_fit_nch.h): scatter kernels per (cell, channel group of 4) + calls
+//   merl_grad_scatter.hpp  what the scatter kernels of the three adjoints share (the two above and merl_rgl_values_grad.hip): the
+//                          wave's merge rule and its record-by-record scatter, fold_source, the f64 add.  Device code only
+//   merl_grad_scatter.hip  grad_scatter_call, the host side of every adjoint call, and the kernel that clears their workspace
 //   merl_update.hip        new values for a resident material in place (include/merl_hip_update.h): table images through the upload's
 //                          build kernels, the row marginal on the device (reduction + finishing kernel), GGX parameters
 //   merl_ggx_grad.hip      the parameter gradient of eval on a GGX conductor (mrl_ggx_grad_batch): reduction kernels + call
@@ -247,6 +250,43 @@ struct DirGradFamily {
 };
 // checks in the order the headers document, then f.launch on the caller's device arrays or chunk by chunk on staged host arrays
 int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f);
+
+// ---- merl_grad_scatter.hip ----
+// An adjoint-of-eval call (include/merl_hip.h mrl_table_grad_batch, merl_hip_fit_table.h, merl_hip_fit_nch.h, merl_hip_fit_rgl.h):
+// a gradient scattered into the measured data of the call's targets, whole arrays or a queue, and what its family supplies
+struct GradScatterCall {
+    const float *wi, *wo, *g;
+    size_t g_bytes;                              // of g per unit
+    const char *g_name;
+    const int32_t *mat;
+    int32_t single_id;
+    size_t n;                                    // units; queued: the queue's capacity
+    bool queued;
+    const uint32_t *queue, *queue_count;
+    const int32_t *target_ids;
+    int n_targets, max_targets;
+    double *out;                                 // the targets' gradients end to end, added to
+};
+struct GradScatterLayout {
+    size_t brick_bytes;                          // of BUF_GRAD_BRICKS; 0: the launch adds straight into `out` — no reserve, no clear, no fold
+    size_t out_doubles;                          // of `out`, over all targets
+    bool nothing_to_add = false;                 // the call is MRL_OK once its arguments are checked; no workspace is touched
+};
+struct GradScatterFamily {
+    std::function<int(int32_t id)> check_target;             // MRL_OK, or the failure (through fail) the family's header documents
+    std::function<int(GradScatterLayout &)> layout;          // after every target passed: fills the family's own descriptors
+    bool refuses_renormalise;                    // MRL_OPT_NEGATIVE = renormalise: MRL_ERR_INVALID
+    // the accumulate kernel on m units at device-accessible arrays: addr[0..2] wi, wo, g and, where the call has one, addr[3] mat;
+    // into the cleared bricks, or (brick_bytes = 0: bricks is null) into out
+    std::function<hipError_t(char *const *addr, size_t m, double *bricks, double *out)> launch;
+    std::function<hipError_t(const double *bricks, double *out)> fold;   // once per call, target by target; not called without bricks
+};
+// checks in the order the headers document; clear, launch and fold on the caller's device arrays, or chunk by chunk on staged host
+// arrays with the sums gathered on the device and added to the caller's on the host.  A queue call copies nothing from host memory
+// at call time and is capturable: so is the clear, which is why it is a kernel (launch_grad_clear)
+int grad_scatter_call(mrl_ctx *ctx, const GradScatterCall &c, const GradScatterFamily &f);
+// zeros `bytes` (a multiple of 16) of gradient bricks with 16-B stores
+hipError_t launch_grad_clear(double *bricks, size_t bytes, int compute_units, hipStream_t stream);
 
 // ---- merl_abi.hip ----
 // a non-blocking stream whose kernels may use all but `reserved` of the device's `device_cus` compute units (reserved = 0: a plain

@@ -5,7 +5,8 @@
 //                       lookup, the clamp mask from the value cell, the three factors of the unit's terms; the wave then transposes
 //                       through LDS so that one wave-instruction carries whole gradient bricks (16 S doubles: four units for S = 1,
 //                       two for S = 2, one for S = 4) as f64 atomic adds.  Lanes of a wave that share a brick are summed first when
-//                       at least kMergeMin share the first live lane's (§5g's wave-uniform rule).
+//                       at least kMergeMin share the first live lane's (§5g's wave-uniform rule; wave_merge_rule / wave_scatter of
+//                       merl_grad_scatter.hpp, which every adjoint's kernel runs).
 //   k_rgl_values_fold   per planar texel: the sum of the brick slots that map to it (rgl::fold_sources, a fixed order), added into
 //                       the caller's array when it is not zero
 //   k_rgl_values_plain<MULTI, INDEXED>  the measured baseline: each lane adds its 12 S terms straight into the planar array
@@ -18,13 +19,13 @@
 #include "merl_ctx.hpp"
 #include "../../include/merl_hip_fit_rgl.h"
 #include "merl_rgl_values_grad.hpp"
+#include "merl_grad_scatter.hpp"
 
 namespace mrl {
 
 namespace {
 
 constexpr int kVgBlock = 256;
-constexpr int kVgMergeMin = 4;           // merge a wave's lanes by brick when at least this many share the first live lane's brick
 constexpr int kVgMaxTargets = MRL_RGL_GRAD_MAX_TARGETS;
 
 // One target of a launch: by value in the kernel arguments (a queue call copies nothing from host memory at call time).  40 B
@@ -47,14 +48,6 @@ struct ValuesGradArgs {
     int n_targets;
     ValuesTarget targets[kVgMaxTargets]; // !MULTI: targets[0] is the launch's material
 };
-
-template <bool INDEXED> __device__ __forceinline__ size_t vg_items(const ValuesGradArgs &a)
-{
-    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }
-    else return a.n;
-}
-
-__device__ __forceinline__ void vg_add(double *p, double v) { (void)unsafeAtomicAdd(p, v); }
 
 // unit i of the launch: its target (by value) and its factors; a unit out of range, of another material or dead is !live
 template <bool MULTI, int MASK>
@@ -100,11 +93,11 @@ __global__ __launch_bounds__(kVgBlock, 2) void k_rgl_values_bricks(ValuesGradArg
     __shared__ unsigned long long s_off[kVgBlock];
     __shared__ double s_f[11][kVgBlock + 1];                    // a[3], ws[4], wc[4]
     // lanes per brick: the launch's own shape, or 64 where shapes mix
-    constexpr unsigned L = MULTI ? 64u : 16u * (unsigned)mask_slices(MASK), U = 64u / L;
+    constexpr unsigned L = MULTI ? 64u : 16u * (unsigned)mask_slices(MASK);
     const unsigned t = threadIdx.x, lane = t & 63u, wbase = t & ~63u;
-    const unsigned sub = lane / L, slot = lane % L;
+    const unsigned slot = lane % L;
     const size_t stride = (size_t)gridDim.x * kVgBlock;
-    const size_t n_items = vg_items<INDEXED>(a);
+    const size_t n_items = grad_items<INDEXED>(a.n, a.idx_count);
     const size_t rounds = (n_items + stride - 1) / stride;       // the same trip count for every thread: barriers inside
     for (size_t rd = 0; rd < rounds; ++rd) {
         const size_t j0 = rd * stride + (size_t)blockIdx.x * kVgBlock + t;
@@ -129,45 +122,12 @@ __global__ __launch_bounds__(kVgBlock, 2) void k_rgl_values_bricks(ValuesGradArg
             return s_f[cc][m] * s_f[3 + kk][m] * s_f[7 + jj][m];
         };
         const uint64_t live = __ballot(key >= 0);
-        if (live != 0ull) {                                      // wave-uniform from here on
-            bool merged = a.merge == 2;
-            if (a.merge == 0) {
-                const int c0 = s_key[wbase + (unsigned)__builtin_ctzll(live)];
-                merged = __popcll(__ballot(key == c0)) >= kVgMergeMin;
-            }
-            if (!merged) {
-                for (unsigned j = 0; j < 64u; j += U) {
-                    if (((live >> j) & ((1ull << U) - 1ull)) == 0ull) continue;
-                    const unsigned m = wbase + j + sub;
-                    if (s_key[m] >= 0) {
-                        const int S = s_slices[m];
-                        if (slot < 12u * (unsigned)S) vg_add(a.bricks + s_off[m] + slot, term(m, S));
-                    }
-                }
-            } else {
-                // leader loop: the lanes that hold the first remaining lane's brick are summed by the slot lanes of each group of L
-                // lanes (its members among the group's own lanes), one atomic per slot and group
-                uint64_t rem = live;
-                while (rem != 0ull) {
-                    const unsigned first = wbase + (unsigned)__builtin_ctzll(rem);
-                    const int c0 = s_key[first];
-                    const uint64_t members = __ballot(key == c0);
-                    rem &= ~members;
-                    const int S = s_slices[first];
-                    uint64_t mm = members;
-                    if constexpr (L < 64u) mm = (members >> (sub * L)) & ((1ull << L) - 1ull);
-                    if (slot < 12u * (unsigned)S && mm != 0ull) {
-                        double acc = 0.0;
-                        while (mm != 0ull) {
-                            const unsigned m = wbase + sub * L + (unsigned)__builtin_ctzll(mm);
-                            mm &= mm - 1ull;
-                            acc += term(m, S);
-                        }
-                        vg_add(a.bricks + s_off[first] + slot, acc);
-                    }
-                }
-            }
-        }
+        // lanes of a wave that share a brick are summed first when many do: a brick's S is that of any of its units
+        wave_scatter<L>(live, wave_merge_rule(a.merge, key, s_key, wbase, live), key, s_key, wbase, lane,
+            [&](unsigned ref) { return slot < 12u * (unsigned)s_slices[ref]; },
+            [&](unsigned m, unsigned ref) { return term(m, s_slices[ref]); },
+            [&](double acc, unsigned m, unsigned ref) { return acc + term(m, s_slices[ref]); },
+            [&](unsigned ref) { return a.bricks + s_off[ref] + slot; });
         __syncthreads();
     }
 }
@@ -177,7 +137,7 @@ __global__ __launch_bounds__(kVgBlock, 2) void k_rgl_values_plain(ValuesGradArgs
 {
 #pragma clang fp contract(off)
     const size_t stride = (size_t)gridDim.x * kVgBlock;
-    const size_t n_items = vg_items<INDEXED>(a);
+    const size_t n_items = grad_items<INDEXED>(a.n, a.idx_count);
     for (size_t j0 = (size_t)blockIdx.x * kVgBlock + threadIdx.x; j0 < n_items; j0 += stride) {
         const size_t i = INDEXED ? (size_t)a.idx[j0] : j0;
         ValuesTarget tg;
@@ -193,7 +153,7 @@ __global__ __launch_bounds__(kVgBlock, 2) void k_rgl_values_plain(ValuesGradArgs
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     const double v = u.a[c] * u.ws[k] * u.wc[jj];
-                    if (k < u.slices && v != 0.0) vg_add(planar + rgl::values_texel(shape, u, c, k, jj), v);
+                    if (k < u.slices && v != 0.0) add_f64(planar + rgl::values_texel(shape, u, c, k, jj), v);
                 }
     }
 }
@@ -332,109 +292,63 @@ bool values_layout(const int *shapes, int n_targets, size_t *planar_off, size_t 
     return true;
 }
 
-int rgl_values_grad(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id, size_t n,
-                    bool queued, const uint32_t *queue, const uint32_t *queue_count, const int32_t *target_ids, int n_targets, double *grad_values)
+// mrl_rgl_values_grad_batch / mrl_rgl_values_grad_queue: the checks, the workspace and the host-array path are grad_scatter_call's
+// (merl_grad_scatter.hip)
+int rgl_values_grad(mrl_ctx *ctx, const GradScatterCall &c)
 {
     if (!ctx) return MRL_ERR_INVALID;
-    MRL_GUARD(ctx);
-    if (n == 0) return MRL_OK;
-    StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
-    if (first_null(streams) || !grad_values || !target_ids || (queued && (!queue || !queue_count))) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    int at_mat = -1;
-    if (mat) { at_mat = (int)streams.size(); streams.push_back({ (void *)mat, 4, false, "mat" }); }
-    if (n_targets < 1 || n_targets > MRL_RGL_GRAD_MAX_TARGETS)
-        return fail(ctx, MRL_ERR_INVALID, "n_targets must be 1.." + std::to_string(MRL_RGL_GRAD_MAX_TARGETS));
-    int shapes[MRL_RGL_GRAD_MAX_TARGETS][5];
-    for (int k = 0; k < n_targets; ++k) {
-        if (!live_id(ctx, target_ids[k]) || ctx->materials[(size_t)target_ids[k]].dev.kind != mrl::KIND_RGL)
-            return fail(ctx, MRL_ERR_MATERIAL, "a target is not a live RGB RGL material (mrl_material_upload_rgl / mrl_material_load_rgl)");
-        for (int j = 0; j < k; ++j)
-            if (target_ids[j] == target_ids[k]) return fail(ctx, MRL_ERR_INVALID, "a material is listed twice among the targets");
-        shape_of(ctx->materials[(size_t)target_ids[k]].rgl, shapes[k]);
-    }
-    size_t planar_off[MRL_RGL_GRAD_MAX_TARGETS + 1], record_base[MRL_RGL_GRAD_MAX_TARGETS], brick_base[MRL_RGL_GRAD_MAX_TARGETS];
-    ValuesLayout all;
-    if (!values_layout(&shapes[0][0], n_targets, planar_off, record_base, brick_base, &all))
-        return fail(ctx, MRL_ERR_INVALID, "the targets have more than 2^31 - 1 workspace records in all");
-    if (queued && n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
-    MRL_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = queued ? common_kind({ grad_values, queue, queue_count }, streams) : common_kind({ grad_values }, streams);
-    if (queued && kind != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
-    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
-
     mrl::ValuesGradArgs a;
     std::memset(&a, 0, sizeof a);
-    a.idx = queue; a.idx_count = queue_count;
-    a.n_targets = n_targets;
-    for (int k = 0; k < n_targets; ++k) {
-        const MaterialHost &mh = ctx->materials[(size_t)target_ids[k]];
-        a.targets[k] = { target_ids[k], mh.rgl.slices(), (int)record_base[k], (const mrl::RglDev *)mh.dev.rgl,
-                         (unsigned long long)brick_base[k], (unsigned long long)planar_off[k] };
-    }
-    // a call without ids: its one material, by value; when that is no target nothing is added
-    mrl::RglDev single{};
-    if (!mat) {
-        int at = -1;
-        for (int k = 0; k < n_targets; ++k) if (target_ids[k] == single_id) at = k;
-        if (at < 0) return MRL_OK;
-        a.targets[0] = a.targets[at];
-        a.n_targets = 1;
-        single = ctx->materials[(size_t)single_id].rgl;
-    }
-    const int variant = ctx->table_grad_kernel;
-    const mrl::ValuesGradChoice choice = mrl::route_values_grad(variant, mat != nullptr, queued, single.n_phi, single.n_theta);
-    const size_t brick_bytes = all.brick_doubles * sizeof(double), planar_doubles = planar_off[n_targets];
-    if (!choice.plain) {
-        DeviceBuf &bricks = ctx->buf[mrl_ctx::BUF_GRAD_BRICKS];
-        const int rc = bricks.reserve(ctx, brick_bytes);
-        if (rc != MRL_OK) return rc;
-        a.bricks = (double *)bricks.p;
-        MRL_HIP(ctx, hipMemsetAsync(a.bricks, 0, brick_bytes, ctx->stream));
-    }
-    auto on = [&](char *const *addr, size_t m) {
-        a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
-        a.mat = at_mat >= 0 ? (const int32_t *)addr[at_mat] : nullptr;
-    };
-    auto fold = [&](double *planar) -> int {
-        if (choice.plain) return MRL_OK;
-        for (int k = 0; k < n_targets; ++k)
-            MRL_HIP(ctx, mrl::launch_values_fold(a.bricks + brick_base[k], planar + planar_off[k], shapes[k], ctx->compute_units, ctx->stream));
-        return MRL_OK;
-    };
-    if (kind == 1) {
-        char *addr[4];
-        for (size_t k = 0; k < streams.size(); ++k) addr[k] = (char *)streams[k].ptr;
-        on(addr, n);
-        a.planar = grad_values;
-        MRL_HIP(ctx, mrl::launch_values_grad(choice, a, single, ctx->compute_units, ctx->stream));
-        return fold(grad_values);
-    }
-    // host arrays: the inputs are staged chunk by chunk, the sums gathered in a device array and added to the caller's on the host
-    double *d_planar = nullptr;
-    MRL_ALLOC(ctx, hipMalloc((void **)&d_planar, planar_doubles * sizeof(double)));
-    auto run = [&]() -> int {
-        MRL_HIP(ctx, hipMemsetAsync(d_planar, 0, planar_doubles * sizeof(double), ctx->stream));
-        a.planar = d_planar;
-        int rc = run_host_staged(ctx, streams, n, 0, [&](char *const *addr, size_t m) -> int {
-            on(addr, m);
-            MRL_HIP(ctx, mrl::launch_values_grad(choice, a, single, ctx->compute_units, ctx->stream));
+    int shapes[MRL_RGL_GRAD_MAX_TARGETS][5];
+    size_t planar_off[MRL_RGL_GRAD_MAX_TARGETS + 1], record_base[MRL_RGL_GRAD_MAX_TARGETS], brick_base[MRL_RGL_GRAD_MAX_TARGETS];
+    mrl::RglDev single{};                                        // a call without ids: its one material, by value
+    mrl::ValuesGradChoice choice{};
+    return grad_scatter_call(ctx, c, {
+        [&](int32_t id) {
+            if (!live_id(ctx, id) || ctx->materials[(size_t)id].dev.kind != mrl::KIND_RGL)
+                return fail(ctx, MRL_ERR_MATERIAL, "a target is not a live RGB RGL material (mrl_material_upload_rgl / mrl_material_load_rgl)");
+            return (int)MRL_OK;
+        },
+        [&](GradScatterLayout &lay) -> int {
+            for (int k = 0; k < c.n_targets; ++k) shape_of(ctx->materials[(size_t)c.target_ids[k]].rgl, shapes[k]);
+            ValuesLayout all;
+            if (!values_layout(&shapes[0][0], c.n_targets, planar_off, record_base, brick_base, &all))
+                return fail(ctx, MRL_ERR_INVALID, "the targets have more than 2^31 - 1 workspace records in all");
+            a.idx = c.queue; a.idx_count = c.queue_count;
+            a.n_targets = c.n_targets;
+            for (int k = 0; k < c.n_targets; ++k) {
+                const MaterialHost &mh = ctx->materials[(size_t)c.target_ids[k]];
+                a.targets[k] = { c.target_ids[k], mh.rgl.slices(), (int)record_base[k], (const mrl::RglDev *)mh.dev.rgl,
+                                 (unsigned long long)brick_base[k], (unsigned long long)planar_off[k] };
+            }
+            // a call without ids: when its material is no target nothing is added
+            if (!c.mat) {
+                int at = -1;
+                for (int k = 0; k < c.n_targets; ++k) if (c.target_ids[k] == c.single_id) at = k;
+                lay.nothing_to_add = at < 0;
+                if (at < 0) return MRL_OK;
+                a.targets[0] = a.targets[at];
+                a.n_targets = 1;
+                single = ctx->materials[(size_t)c.single_id].rgl;
+            }
+            choice = mrl::route_values_grad(ctx->table_grad_kernel, c.mat != nullptr, c.queued, single.n_phi, single.n_theta);
+            lay.brick_bytes = choice.plain ? 0 : all.brick_doubles * sizeof(double);
+            lay.out_doubles = planar_off[c.n_targets];
             return MRL_OK;
-        });
-        if (rc != MRL_OK) return rc;
-        rc = fold(d_planar);
-        if (rc != MRL_OK) return rc;
-        std::vector<double> sums;
-        try { sums.resize(planar_doubles); } catch (const std::bad_alloc &) { return fail(ctx, MRL_ERR_OOM, "gradient buffer"); }
-        MRL_HIP(ctx, hipMemcpyAsync(sums.data(), d_planar, planar_doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MRL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t t = 0; t < planar_doubles; ++t)
-            if (sums[t] != 0.0) grad_values[t] += sums[t];
-        return MRL_OK;
-    };
-    const int rc = run();
-    if (rc != MRL_OK) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_planar);
-    return rc;
+        },
+        false,
+        [&](char *const *addr, size_t m, double *bricks, double *out) {
+            a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
+            a.mat = c.mat ? (const int32_t *)addr[3] : nullptr;
+            a.bricks = bricks; a.planar = out;
+            return mrl::launch_values_grad(choice, a, single, ctx->compute_units, ctx->stream);
+        },
+        [&](const double *bricks, double *out) {
+            hipError_t e = hipSuccess;
+            for (int k = 0; k < c.n_targets && e == hipSuccess; ++k)
+                e = mrl::launch_values_fold(bricks + brick_base[k], out + planar_off[k], shapes[k], ctx->compute_units, ctx->stream);
+            return e;
+        } });
 }
 
 } // namespace
@@ -444,14 +358,16 @@ extern "C" {
 int mrl_rgl_values_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id, size_t n,
                               const int32_t *target_ids, int n_targets, double *grad_values)
 {
-    return rgl_values_grad(ctx, wi, wo, grad_rgb, mat, single_id, n, false, nullptr, nullptr, target_ids, n_targets, grad_values);
+    return rgl_values_grad(ctx, { wi, wo, grad_rgb, 12, "grad_rgb", mat, single_id, n, false, nullptr, nullptr, target_ids, n_targets,
+                                  MRL_RGL_GRAD_MAX_TARGETS, grad_values });
 }
 
 int mrl_rgl_values_grad_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id,
                               const uint32_t *queue, const uint32_t *queue_count, size_t capacity, const int32_t *target_ids, int n_targets,
                               double *grad_values)
 {
-    return rgl_values_grad(ctx, wi, wo, grad_rgb, mat, single_id, capacity, true, queue, queue_count, target_ids, n_targets, grad_values);
+    return rgl_values_grad(ctx, { wi, wo, grad_rgb, 12, "grad_rgb", mat, single_id, capacity, true, queue, queue_count, target_ids, n_targets,
+                                  MRL_RGL_GRAD_MAX_TARGETS, grad_values });
 }
 
 int mrl_rgl_values_shape(const mrl_ctx *ctx, int id, int shape[5])

@@ -5,7 +5,8 @@
 // serves both table layouts.
 //   k_grad_bricks   one lane = one unit: the f64 coordinate transform of eval, the Float corner weights; the wave then transposes
 //                   through LDS so that one wave-instruction carries the 24 values of two units (two contiguous 192-B segments of
-//                   the gradient bricks) as f64 atomic adds.  Lanes of a wave that share a cell are summed first when many do.
+//                   the gradient bricks) as f64 atomic adds.  Lanes of a wave that share a cell are summed first when many do
+//                   (wave_merge_rule / wave_scatter of merl_grad_scatter.hpp, which every adjoint's kernel runs).
 //   k_grad_fold     per texel: the sum of the brick slots that map to it (clamp / wrap folding), added into the caller's planar array
 //   k_grad_naive    the A/B baseline: each lane adds its 24 values straight into the planar array (64 lanes, 64 rows)
 // Gradient brick of cell (h0, d0, p0): 32 doubles, slot 3 k + ch for corner k = 4 a + 2 b + c (corner_weights' order), 24 used.
@@ -17,6 +18,7 @@
 #include "merl_ctx.hpp"
 #include "../../include/merl_hip_fit_table.h"
 #include "merl_table_fast.hpp"
+#include "merl_grad_scatter.hpp"
 
 namespace mrl {
 
@@ -24,7 +26,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kBrickSlots = 32;          // doubles per gradient brick (256 B)
-constexpr int kMergeMin = 4;             // merge a wave's lanes by cell when at least this many share the first live lane's cell
 
 // One target table of a launch with material ids: what the kernels need of it, by value in the kernel arguments (a queue call is
 // capturable in a HIP graph: nothing is copied from host memory at call time).  48 B
@@ -79,15 +80,6 @@ __device__ __forceinline__ GradShape target_shape(const GradArgs &a, int id)
     }
     return s;
 }
-template <bool INDEXED> __device__ __forceinline__ size_t grad_items(const GradArgs &a)
-{
-    if constexpr (INDEXED) { const size_t c = (size_t)*a.idx_count; return c < a.n ? c : a.n; }      // every thread reads the same count
-    else return a.n;
-}
-
-// f64 add without a compare-and-swap loop (global_atomic_add_f64 / flat_atomic_add_f64); the destinations are device allocations
-__device__ __forceinline__ void add_f64(double *p, double v) { (void)unsafeAtomicAdd(p, v); }
-
 // What unit i adds: the cell of its lookup (eval's own TableCell, kept inside the table; the kernels read its indices only), whether
 // eval masks the unit, the Float corner weights and, per channel, scale x (cos(theta_o) or 1) x g in f64.  Masking is a select: a dead unit's g may be NaN.
 struct GradUnit {
@@ -154,12 +146,12 @@ __device__ __forceinline__ void grad_bricks(const GradArgs &a)
     GradShape shape = single_shape(a);                           // !PER_LANE: wave-uniform, formed once
     fast::TableMaps maps(shape.n_th, shape.n_td, shape.n_pd, shape.param);
     const unsigned t = threadIdx.x, lane = t & 63u, wbase = t & ~63u;
-    const unsigned sub = lane >> 5, slot = lane & 31u;           // two units per wave-instruction, 32 slots each (24 used)
+    const unsigned slot = lane & 31u;                            // two units per wave-instruction, 32 slots each (24 used)
     const unsigned k = slot / 3u, ch = slot - 3u * k;
     const bool slot_on = slot < (LOOKUP ? 24u : 3u);             // a nearest lookup has corner 0 only
     const unsigned kk = slot_on ? k : 0u, cc = slot_on ? ch : 0u;
     const size_t stride = (size_t)gridDim.x * kBlock;
-    const size_t n_items = grad_items<INDEXED>(a);
+    const size_t n_items = grad_items<INDEXED>(a.n, a.idx_count);
     const size_t rounds = (n_items + stride - 1) / stride;       // the same trip count for every thread: barriers inside
     for (size_t r = 0; r < rounds; ++r) {
         const size_t j = r * stride + (size_t)blockIdx.x * kBlock + t;
@@ -176,40 +168,12 @@ __device__ __forceinline__ void grad_bricks(const GradArgs &a)
         s_s[0][t] = u.s[0]; s_s[1][t] = u.s[1]; s_s[2][t] = u.s[2];
         __syncthreads();
         const uint64_t live = __ballot(cell >= 0);
-        if (live != 0ull) {                                      // wave-uniform from here on
-            bool merged = a.merge == 2;
-            if (a.merge == 0) {
-                const int c0 = s_cell[wbase + (unsigned)__builtin_ctzll(live)];
-                merged = __popcll(__ballot(cell == c0)) >= kMergeMin;
-            }
-            if (!merged) {
-                for (unsigned j = 0; j < 64u; j += 2u) {
-                    if (((live >> j) & 3ull) == 0ull) continue;
-                    const unsigned m = wbase + j + sub;
-                    const int cm = s_cell[m];
-                    if (slot_on && cm >= 0) add_f64(a.bricks + (size_t)cm * kBrickSlots + slot, (double)s_w[kk][m] * s_s[cc][m]);
-                }
-            } else {
-                // leader loop: the lanes that hold the first remaining lane's cell are summed by the 24 slot lanes of each half
-                // (low half: members among lanes 0..31, high half: among 32..63), one atomic per slot and half
-                uint64_t rem = live;
-                while (rem != 0ull) {
-                    const int c0 = s_cell[wbase + (unsigned)__builtin_ctzll(rem)];
-                    const uint64_t members = __ballot(cell == c0);
-                    rem &= ~members;
-                    uint32_t mm = sub ? (uint32_t)(members >> 32) : (uint32_t)members;
-                    if (slot_on && mm != 0u) {
-                        double acc = 0.0;
-                        while (mm != 0u) {
-                            const unsigned m = wbase + 32u * sub + (unsigned)__builtin_ctz(mm);
-                            mm &= mm - 1u;
-                            acc = __builtin_fma((double)s_w[kk][m], s_s[cc][m], acc);
-                        }
-                        add_f64(a.bricks + (size_t)c0 * kBrickSlots + slot, acc);
-                    }
-                }
-            }
-        }
+        // lanes of a wave that share a cell are summed first when many do: an fma chain over a cell's members, one atomic per slot
+        wave_scatter<32>(live, wave_merge_rule(a.merge, cell, s_cell, wbase, live), cell, s_cell, wbase, lane,
+            [&](unsigned) { return slot_on; },
+            [&](unsigned m, unsigned) { return (double)s_w[kk][m] * s_s[cc][m]; },
+            [&](double acc, unsigned m, unsigned) { return __builtin_fma((double)s_w[kk][m], s_s[cc][m], acc); },
+            [&](unsigned ref) { return a.bricks + (size_t)s_cell[ref] * kBrickSlots + slot; });
         __syncthreads();
     }
 }
@@ -218,15 +182,6 @@ template <int LOOKUP>
 __global__ __launch_bounds__(kBlock) void k_grad_bricks(GradArgs a) { grad_bricks<LOOKUP, false, false>(a); }
 template <int LOOKUP, bool INDEXED>
 __global__ __launch_bounds__(kBlock) void k_grad_bricks_mat(GradArgs a) { grad_bricks<LOOKUP, true, INDEXED>(a); }
-
-// the brick slots that reach texel i of an axis of n texels: source s = 0: cell i, corner offset 0; 1: cell i - 1, offset 1;
-// 2: the folded corner index n — cell n - 1, offset 1 — onto texel n - 1 (clamped axis) or texel 0 (periodic axis)
-__device__ __forceinline__ bool fold_source(int s, int i, int n, bool periodic, int &cell, int &off)
-{
-    cell = s == 0 ? i : (s == 1 ? i - 1 : n - 1);
-    off = s == 0 ? 0 : 1;
-    return s == 0 ? true : (s == 1 ? i >= 1 : (periodic ? i == 0 : i == n - 1));
-}
 
 __global__ __launch_bounds__(kBlock) void k_grad_fold(const double *bricks, double *planar, int n_th, int n_td, int n_pd, int periodic_phi)
 {
@@ -267,7 +222,7 @@ __device__ __forceinline__ void grad_naive(const GradArgs &a)
     GradShape shape = single_shape(a);
     fast::TableMaps maps(shape.n_th, shape.n_td, shape.n_pd, shape.param);
     const size_t stride = (size_t)gridDim.x * kBlock;
-    const size_t n_items = grad_items<INDEXED>(a);
+    const size_t n_items = grad_items<INDEXED>(a.n, a.idx_count);
     for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < n_items; j += stride) {
         const size_t i = INDEXED ? (size_t)a.idx[j] : j;
         unit_table<PER_LANE>(a, i, true, shape, maps);
@@ -337,70 +292,6 @@ using namespace mrlabi;
 
 namespace {
 
-// One table of a call: its bricks start at cell_base records into the workspace, its planar array at 3 cell_base doubles
-struct GradTable { int dims[3]; int param; size_t cell_base; };
-
-// What every table-gradient call does once its arguments are checked.  streams: wi, wo, grad_rgb and (at_mat >= 0) mat; kind: 1 device
-// pointers, 0 host arrays; a: everything but the arrays (a.idx: a queue — device pointers only); tables: the call's tables, `cells`
-// cells in all.  The workspace is cleared once and folded once, table by table, into the tables' own slices and nothing else.
-int run_table_grad(mrl_ctx *ctx, mrl::GradArgs a, const StreamList &streams, int at_mat, size_t n, const std::vector<GradTable> &tables, size_t cells,
-                   double *grad_planar, int kind)
-{
-    const int variant = ctx->table_grad_kernel;
-    if (variant != 1) {
-        DeviceBuf &bricks = ctx->buf[mrl_ctx::BUF_GRAD_BRICKS];      // one 256-B record per table cell; grown on demand, reused
-        const int rc = bricks.reserve(ctx, cells * mrl::kBrickSlots * sizeof(double));
-        if (rc != MRL_OK) return rc;
-        a.bricks = (double *)bricks.p;
-        MRL_HIP(ctx, hipMemsetAsync(a.bricks, 0, cells * mrl::kBrickSlots * sizeof(double), ctx->stream));
-    }
-    auto on = [&](char *const *addr, size_t m) {
-        a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
-        a.mat = at_mat >= 0 ? (const int32_t *)addr[at_mat] : nullptr;
-    };
-    auto fold = [&](double *planar) -> int {
-        if (variant == 1) return MRL_OK;
-        for (const GradTable &t : tables)
-            MRL_HIP(ctx, mrl::launch_table_grad_fold(a.bricks + t.cell_base * mrl::kBrickSlots, planar + 3 * t.cell_base, t.dims, t.param,
-                                                     ctx->compute_units, ctx->stream));
-        return MRL_OK;
-    };
-    if (kind == 1) {
-        char *addr[4];
-        for (size_t k = 0; k < streams.size(); ++k) addr[k] = (char *)streams[k].ptr;
-        on(addr, n);
-        a.planar = grad_planar;
-        MRL_HIP(ctx, mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream));
-        return fold(grad_planar);
-    }
-    // host arrays: the inputs are staged chunk by chunk, the sums gathered in a device array and added to the caller's on the host
-    double *d_planar = nullptr;
-    MRL_ALLOC(ctx, hipMalloc((void **)&d_planar, 3 * cells * sizeof(double)));
-    auto run = [&]() -> int {
-        MRL_HIP(ctx, hipMemsetAsync(d_planar, 0, 3 * cells * sizeof(double), ctx->stream));
-        a.planar = d_planar;
-        int rc = run_host_staged(ctx, streams, n, 0, [&](char *const *addr, size_t m) -> int {
-            on(addr, m);
-            MRL_HIP(ctx, mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream));
-            return MRL_OK;
-        });
-        if (rc != MRL_OK) return rc;
-        rc = fold(d_planar);
-        if (rc != MRL_OK) return rc;
-        std::vector<double> sums;
-        try { sums.resize(3 * cells); } catch (const std::bad_alloc &) { return fail(ctx, MRL_ERR_OOM, "gradient buffer"); }
-        MRL_HIP(ctx, hipMemcpyAsync(sums.data(), d_planar, 3 * cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MRL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t t = 0; t < 3 * cells; ++t)
-            if (sums[t] != 0.0) grad_planar[t] += sums[t];
-        return MRL_OK;
-    };
-    const int rc = run();
-    if (rc != MRL_OK) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_planar);
-    return rc;
-}
-
 // is `id` a table the adjoint is defined for?  MRL_OK, or the failure mrl_table_grad_batch documents
 int check_grad_table(mrl_ctx *ctx, int32_t id)
 {
@@ -412,55 +303,64 @@ int check_grad_table(mrl_ctx *ctx, int32_t id)
     return MRL_OK;
 }
 
-// mrl_table_grad_batch_mat / mrl_table_grad_queue (include/merl_hip_fit_table.h); queued: over queue[0 .. min(*queue_count, n)), n its capacity
-int table_grad_targets(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id, size_t n,
-                       bool queued, const uint32_t *queue, const uint32_t *queue_count, const int32_t *target_ids, int n_targets, double *grad_planar)
+// Every table-gradient call: the checks, the workspace and the host-array path are grad_scatter_call's (merl_grad_scatter.hip).
+// with_targets: mrl_table_grad_batch_mat / mrl_table_grad_queue (include/merl_hip_fit_table.h); without: mrl_table_grad_batch, whose
+// one table c.target_ids[0] names — the kernels without target descriptors, and no bound on the cells beyond the table's own
+int table_grad(mrl_ctx *ctx, const GradScatterCall &c, bool with_targets)
 {
     if (!ctx) return MRL_ERR_INVALID;
-    MRL_GUARD(ctx);
-    if (n == 0) return MRL_OK;
-    StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
-    if (first_null(streams) || !grad_planar || !target_ids || (queued && (!queue || !queue_count))) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    int at_mat = -1;
-    if (mat) { at_mat = (int)streams.size(); streams.push_back({ (void *)mat, 4, false, "mat" }); }
-    if (n_targets < 1 || n_targets > MRL_TABLE_GRAD_MAX_TARGETS)
-        return fail(ctx, MRL_ERR_INVALID, "n_targets must be 1.." + std::to_string(MRL_TABLE_GRAD_MAX_TARGETS));
     mrl::GradArgs a;
     std::memset(&a, 0, sizeof a);
-    int dims[MRL_TABLE_GRAD_MAX_TARGETS][3];
-    for (int k = 0; k < n_targets; ++k) {
-        const int rc = check_grad_table(ctx, target_ids[k]);
-        if (rc != MRL_OK) return rc;
-        for (int j = 0; j < k; ++j)
-            if (target_ids[j] == target_ids[k]) return fail(ctx, MRL_ERR_INVALID, "a material is listed twice among the targets");
-        const MaterialHost &mh = ctx->materials[(size_t)target_ids[k]];
-        mrl::GradTarget &t = a.targets[k];
-        t.id = target_ids[k];
-        dims[k][0] = t.n_th = mh.dev.n_th; dims[k][1] = t.n_td = mh.dev.n_td; dims[k][2] = t.n_pd = mh.dev.n_pd; t.param = mh.dev.param;
-        t.scale[0] = mh.scale[0]; t.scale[1] = mh.scale[1]; t.scale[2] = mh.scale[2];
-    }
-    // where each target's bricks and planar array start: the one place that adds the cells up and bounds the int global cell index
-    size_t offsets[MRL_TABLE_GRAD_MAX_TARGETS + 1];
-    if (mrl_table_grad_layout(&dims[0][0], n_targets, offsets) != MRL_OK)
-        return fail(ctx, MRL_ERR_INVALID, "the targets have more than 2^31 - 1 cells in all");
-    std::vector<GradTable> tables;
-    for (int k = 0; k < n_targets; ++k) {
-        a.targets[k].cell_base = (int)(offsets[k] / 3);
-        tables.push_back({ { dims[k][0], dims[k][1], dims[k][2] }, a.targets[k].param, offsets[k] / 3 });
-    }
-    const size_t cells = offsets[n_targets] / 3;
-    a.n_targets = n_targets;
-    if (ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
-        return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise makes eval non-linear in the table: no adjoint");
-    if (queued && n > ((size_t)1 << 32)) return fail(ctx, MRL_ERR_INVALID, "queue capacity exceeds 2^32 (indices are uint32)");
-    MRL_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = queued ? common_kind({ grad_planar, queue, queue_count }, streams) : common_kind({ grad_planar }, streams);
-    if (queued && kind != 1) return fail(ctx, MRL_ERR_POINTER_MIX, "queue calls take device pointers only");
-    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
-    a.opts = ctx->opts;
-    a.single_id = single_id;
-    a.idx = queue; a.idx_count = queue_count;
-    return run_table_grad(ctx, a, streams, at_mat, n, tables, cells, grad_planar, kind);
+    int variant = 0;
+    return grad_scatter_call(ctx, c, {
+        [&](int32_t id) { return check_grad_table(ctx, id); },
+        [&](GradScatterLayout &lay) -> int {
+            int dims[MRL_TABLE_GRAD_MAX_TARGETS][3];
+            for (int k = 0; k < c.n_targets; ++k) {
+                const MaterialHost &mh = ctx->materials[(size_t)c.target_ids[k]];
+                mrl::GradTarget &t = a.targets[k];
+                t.id = c.target_ids[k];
+                dims[k][0] = t.n_th = mh.dev.n_th; dims[k][1] = t.n_td = mh.dev.n_td; dims[k][2] = t.n_pd = mh.dev.n_pd; t.param = mh.dev.param;
+                t.scale[0] = mh.scale[0]; t.scale[1] = mh.scale[1]; t.scale[2] = mh.scale[2];
+            }
+            // where each target's bricks (cell_base records into the workspace) and planar array (3 cell_base doubles into out) start:
+            // the one place that adds the cells up and bounds the int global cell index.  The single table starts at 0
+            size_t offsets[MRL_TABLE_GRAD_MAX_TARGETS + 1] = { 0, 3 * (size_t)dims[0][0] * dims[0][1] * dims[0][2] };
+            if (with_targets && mrl_table_grad_layout(&dims[0][0], c.n_targets, offsets) != MRL_OK)
+                return fail(ctx, MRL_ERR_INVALID, "the targets have more than 2^31 - 1 cells in all");
+            for (int k = 0; k < c.n_targets; ++k) a.targets[k].cell_base = (int)(offsets[k] / 3);
+            const size_t cells = offsets[c.n_targets] / 3;
+            if (with_targets) a.n_targets = c.n_targets;
+            else {                                                   // the kernels without targets read the table from the arguments' head
+                const mrl::GradTarget &t = a.targets[0];
+                a.n_th = t.n_th; a.n_td = t.n_td; a.n_pd = t.n_pd; a.param = t.param;
+                a.scale[0] = t.scale[0]; a.scale[1] = t.scale[1]; a.scale[2] = t.scale[2];
+            }
+            a.opts = ctx->opts;
+            a.single_id = c.single_id;
+            a.idx = c.queue; a.idx_count = c.queue_count;
+            variant = ctx->table_grad_kernel;
+            lay.brick_bytes = variant == 1 ? 0 : cells * mrl::kBrickSlots * sizeof(double);      // one 256-B record per table cell
+            lay.out_doubles = 3 * cells;
+            return MRL_OK;
+        },
+        true,
+        [&](char *const *addr, size_t m, double *bricks, double *out) {
+            a.wi = (const float *)addr[0]; a.wo = (const float *)addr[1]; a.g = (const float *)addr[2]; a.n = m;
+            a.mat = c.mat ? (const int32_t *)addr[3] : nullptr;
+            a.bricks = bricks; a.planar = out;
+            return mrl::launch_table_grad(a, variant, ctx->compute_units, ctx->stream);
+        },
+        [&](const double *bricks, double *out) {
+            hipError_t e = hipSuccess;
+            for (int k = 0; k < c.n_targets && e == hipSuccess; ++k) {
+                const mrl::GradTarget &t = a.targets[k];
+                const int dims[3] = { t.n_th, t.n_td, t.n_pd };
+                e = mrl::launch_table_grad_fold(bricks + (size_t)t.cell_base * mrl::kBrickSlots, out + 3 * (size_t)t.cell_base, dims, t.param,
+                                                ctx->compute_units, ctx->stream);
+            }
+            return e;
+        } });
 }
 
 } // namespace
@@ -469,27 +369,7 @@ extern "C" {
 
 int mrl_table_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, int32_t id, size_t n, double *grad_planar)
 {
-    if (!ctx) return MRL_ERR_INVALID;
-    MRL_GUARD(ctx);
-    if (n == 0) return MRL_OK;
-    const StreamList streams = { { (void *)wi, 12, false, "wi" }, { (void *)wo, 12, false, "wo" }, { (void *)grad_rgb, 12, false, "grad_rgb" } };
-    if (first_null(streams) || !grad_planar) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    int rc = check_grad_table(ctx, id);
-    if (rc != MRL_OK) return rc;
-    const MaterialHost &mh = ctx->materials[(size_t)id];
-    if (ctx->opts.negative == mrl::NEGATIVE_RENORMALISE)
-        return fail(ctx, MRL_ERR_INVALID, "MRL_OPT_NEGATIVE = renormalise makes eval non-linear in the table: no adjoint");
-    MRL_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = common_kind({ grad_planar }, streams);
-    if (kind < 0) return fail(ctx, MRL_ERR_POINTER_MIX, "host and device pointers mixed in one call");
-
-    mrl::GradArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_th = mh.dev.n_th; a.n_td = mh.dev.n_td; a.n_pd = mh.dev.n_pd; a.param = mh.dev.param;
-    a.opts = ctx->opts;
-    a.scale[0] = mh.scale[0]; a.scale[1] = mh.scale[1]; a.scale[2] = mh.scale[2];
-    const size_t plane = (size_t)a.n_th * a.n_td * a.n_pd;
-    return run_table_grad(ctx, a, streams, -1, n, { { { a.n_th, a.n_td, a.n_pd }, a.param, 0 } }, plane, grad_planar, kind);
+    return table_grad(ctx, { wi, wo, grad_rgb, 12, "grad_rgb", nullptr, id, n, false, nullptr, nullptr, &id, 1, 1, grad_planar }, false);
 }
 
 int mrl_table_grad_layout(const int *dims, int n_targets, size_t *offsets_out)
@@ -512,15 +392,16 @@ int mrl_table_grad_layout(const int *dims, int n_targets, size_t *offsets_out)
 int mrl_table_grad_batch_mat(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id, size_t n,
                              const int32_t *target_ids, int n_targets, double *grad_planar)
 {
-    return table_grad_targets(ctx, wi, wo, grad_rgb, mat, single_id, n, false, nullptr, nullptr, target_ids, n_targets, grad_planar);
+    return table_grad(ctx, { wi, wo, grad_rgb, 12, "grad_rgb", mat, single_id, n, false, nullptr, nullptr, target_ids, n_targets,
+                             MRL_TABLE_GRAD_MAX_TARGETS, grad_planar }, true);
 }
 
 int mrl_table_grad_queue(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb, const int32_t *mat, int32_t single_id,
                          const uint32_t *queue, const uint32_t *queue_count, size_t capacity, const int32_t *target_ids, int n_targets,
                          double *grad_planar)
 {
-    return table_grad_targets(ctx, wi, wo, grad_rgb, mat, single_id, capacity, true, queue, queue_count, target_ids, n_targets, grad_planar);
+    return table_grad(ctx, { wi, wo, grad_rgb, 12, "grad_rgb", mat, single_id, capacity, true, queue, queue_count, target_ids, n_targets,
+                             MRL_TABLE_GRAD_MAX_TARGETS, grad_planar }, true);
 }
 
 } // extern "C"
-

@@ -214,24 +214,26 @@ def test_queue_form_equals_the_batch_form_on_the_gathered_units(lookup, node):
         for k, (_, S) in enumerate(refs):
             _same(twice[k], single[k] + extra[k], S, f"doubled slot, target {k}", worst)
         assert any(np.abs(e).max() > 0 for e in extra)
-        # one capture (single stream, no parallel branches), replayed with another device-side count
+        # one capture (single stream, no parallel branches), replayed with other device-side counts: more than once, which is why
+        # the call clears its workspace with a kernel ("What the adjoints share") — _check asks for exact zeros where S = 0
         out = torch.zeros(total, dtype=torch.float64, device="cuda")
         count.fill_(600)
         torch.cuda.synchronize()
         graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
         with torch.cuda.graph(graph, stream=side):
             gpu.table_grad_queue(dwi, dwo, dg, queue, count, targets, mat=dmat, out=out)
-        out.zero_()
-        count.fill_(300)
-        graph.replay()
-        torch.cuda.synchronize()
-        direct = _np(gpu.table_grad_queue(dwi, dwo, dg, queue, count, targets, mat=dmat))
-        refs = inp.reference(wi[slots[:300]], wo[slots[:300]], g[slots[:300]], role[slots[:300]], inp.MIXED, lookup, node)
-        at, replayed = 0, out.cpu().numpy()
-        for k, (R, S) in enumerate(refs):
-            G = replayed[at:at + R.size].reshape(R.shape); at += R.size
-            _check(G, R, S, f"graph replay, target {k}")
-            _same(G, direct[k], S, f"graph replay against the direct call, target {k}", worst)
+        for c in (300, inp.BASE):
+            out.zero_()
+            count.fill_(c)
+            graph.replay()
+            torch.cuda.synchronize()
+            direct = _np(gpu.table_grad_queue(dwi, dwo, dg, queue, count, targets, mat=dmat))
+            refs = inp.reference(wi[slots[:c]], wo[slots[:c]], g[slots[:c]], role[slots[:c]], inp.MIXED, lookup, node)
+            at, replayed = 0, out.cpu().numpy()
+            for k, (R, S) in enumerate(refs):
+                G = replayed[at:at + R.size].reshape(R.shape); at += R.size
+                _check(G, R, S, f"graph replay, count {c} target {k}")
+                _same(G, direct[k], S, f"graph replay against the direct call, count {c} target {k}", worst)
         gpu.use_own_stream()
 
 

@@ -131,3 +131,15 @@ def test_table_grad_kernels_keep_registers_and_add_with_f64_atomics():
         atomics = set(re.findall(r"\b((?:global|flat|buffer)_atomic_\w+)", kernels[name][1]))
         assert atomics == {"global_atomic_add_f64"}, (name, atomics)
     assert not re.search(r"_atomic_", kernels["k_grad_fold"][1])
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc missing")
+def test_the_shared_clear_is_the_one_kernel_of_its_unit_and_stores_plainly():
+    """merl_grad_scatter.hip: the host call the adjoints share and the kernel that clears their workspace (a kernel, so that a
+    captured call replays; DESIGN.md, "What the adjoints share")."""
+    import isa_round_trips as irt
+    kernels = _kernels(irt.compile_to_asm(os.path.join(ROOT, "mitsuba_customization_amd", "csrc", "merl_grad_scatter.hip")))
+    assert set(kernels) == {"k_grad_clear"}, sorted(kernels)
+    scratch, text = kernels["k_grad_clear"]
+    assert scratch == 0
+    assert not re.search(r"_atomic_", text)
