@@ -2,7 +2,9 @@
 // product's image builder (csrc/merl_rgl.hip) compiled for the HOST, so that tests/test_rgl_dir_grad_cpu.py can hold the direction
 // gradient of eval on an RGL material to its reference in a container without a GPU.  No HIP runtime call is made.  Built by the
 // test with hipcc.  Modelled on tests/rgl_host_harness.hip.
-//   usage: rgl_dir_grad_host_harness <fields.bin> <units.bin> <out.bin>
+//   usage: rgl_dir_grad_host_harness <fields.bin> <units.bin> <out.bin> [mask]
+//   mask: the per-lane function instantiated for the file's own bracket shape (MASK 1 / 3 / 5 / 15, what the single-material kernels
+//         run) instead of MASK 0 (the shape tested at run time, what the id kernels run)
 //   fields.bin: int32 n_phi n_theta nx ny ndf_nx ndf_ny sigma_nx sigma_ny jacobian, then phi_i theta_i ndf sigma vndf luminance rgb (float32);
 //               every table [..][ny][nx]
 //   units.bin:  uint64 n, then wi[n][3] wo[n][3] g[n][3];   out.bin: grad_wi[n][3] grad_wo[n][3] eval[n][3] (float32)
@@ -11,6 +13,8 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
 
 int main(int argc, char **argv)
 {
@@ -43,8 +47,20 @@ int main(int argc, char **argv)
     if (std::fread(wi.data(), 4, 3 * n, f) != 3 * n || std::fread(wo.data(), 4, 3 * n, f) != 3 * n || std::fread(g.data(), 4, 3 * n, f) != 3 * n) return 3;
     std::fclose(f);
     const mrl::rgl::GridMem grids{ r.phi, r.theta, r.wavelengths };
+    const bool own = argc >= 5 && !std::strcmp(argv[4], "mask");
+    const int mask = own ? (1 | (r.n_phi > 1 ? 2 : 0) | (r.n_theta > 1 ? 4 : 0) | (r.n_phi > 1 && r.n_theta > 1 ? 8 : 0)) : 0;
+    auto unit = [&](auto m, size_t i) {
+        return mrl::rgl::eval_dir_grad<decltype(m)::value>(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], &g[3 * i]);
+    };
     for (size_t i = 0; i < n; ++i) {
-        const mrl::rgl::RglDirGrad d = mrl::rgl::eval_dir_grad(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], &g[3 * i]);
+        mrl::rgl::RglDirGrad d;
+        switch (mask) {
+        case 1:  d = unit(std::integral_constant<int, 1>{}, i); break;
+        case 3:  d = unit(std::integral_constant<int, 3>{}, i); break;
+        case 5:  d = unit(std::integral_constant<int, 5>{}, i); break;
+        case 15: d = unit(std::integral_constant<int, 15>{}, i); break;
+        default: d = unit(std::integral_constant<int, 0>{}, i); break;
+        }
         float pdf;
         for (int k = 0; k < 3; ++k) { out[3 * i + k] = d.wi[k]; out[3 * n + 3 * i + k] = d.wo[k]; }
         mrl::rgl::eval_pdf<true, false>(r, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], &out[6 * n + 3 * i], pdf);
@@ -52,6 +68,6 @@ int main(int argc, char **argv)
     f = std::fopen(argv[3], "wb");
     if (!f || std::fwrite(out.data(), 4, out.size(), f) != out.size()) return 5;
     std::fclose(f);
-    std::printf("rgl direction-gradient host harness ok: %llu units\n", n);
+    std::printf("rgl direction-gradient host harness ok: %llu units, MASK %d\n", n, mask);
     return 0;
 }

@@ -219,7 +219,7 @@ FILES = {
     "iso": lambda: _synth(seed=51, n_phi=1, n_theta=6, res=12),
     "iso_nojac": lambda: dict(_synth(seed=51, n_phi=1, n_theta=6, res=12), jacobian=np.array([0], np.uint8)),
     "iso_theta1": lambda: _synth(seed=52, n_phi=1, n_theta=1, res=12),
-    "iso_phi2": lambda: _synth(seed=53, n_phi=2, n_theta=3, res=12),
+    "iso_phi2": lambda: _synth(seed=53, n_phi=2, n_theta=3, res=12),           # 2 x 3 nodes: both brackets, a mask-15 file (phi_only: mask 3)
     "aniso": lambda: _synth(seed=54, n_phi=8, n_theta=4, res=(12, 10)),
     "aniso_red2": lambda: _synth(seed=55, n_phi=8, n_theta=4, res=(12, 10), reduction=2),
     "aniso_red4": lambda: _synth(seed=56, n_phi=8, n_theta=4, res=(12, 10), reduction=4),
@@ -228,8 +228,17 @@ FILES = {
     "iso_cols": lambda: _synth(seed=59, n_phi=1, n_theta=6, res=12, sparse="cols"),
     "iso_negative": lambda: _negative_band(_synth(seed=51, n_phi=1, n_theta=6, res=12)),
     "ggx_res32": _ggx,
+    # n_phi > 1, n_theta == 1: the bracket shape the backward kernels compile as MASK 3 (appended: a file's index seeds its units)
+    "phi_only": lambda: _synth(seed=60, n_phi=5, n_theta=1, res=(12, 10)),
+    "phi_only_uneven": lambda: _synth(seed=61, n_phi=5, n_theta=1, res=(12, 10), grid="uneven"),
 }
 FILE_NAMES = tuple(FILES)
+
+
+def file_mask(fields):
+    """find_slices' mask of a file: 1 one slice, 3 phi brackets only, 5 theta brackets only, 15 both — the MASK its kernels compile for"""
+    n_phi, n_theta = np.asarray(fields["vndf"]).shape[:2]
+    return 1 | (2 if n_phi > 1 else 0) | (4 if n_theta > 1 else 0) | (8 if n_phi > 1 and n_theta > 1 else 0)
 
 
 def fixed_block(theta_nodes):
@@ -313,15 +322,18 @@ def write_fields(path, f):
             np.ascontiguousarray(f[k], np.float32).tofile(o)
 
 
-def run_harness(build, tmp, fields, wi, wo, g):
-    """the host-compiled per-lane function: (grad_wi, grad_wo, eval) [n, 3] f32 each"""
+def run_harness(build, tmp, fields, wi, wo, g, own_mask=False):
+    """the host-compiled per-lane function: (grad_wi, grad_wo, eval) [n, 3] f32 each.  own_mask: instantiated for the file's bracket
+    shape (MASK = file_mask(fields), the single-material kernels' form) instead of MASK 0"""
     n = len(wi)
     write_fields(tmp / "f.bin", fields)
     with open(tmp / "u.bin", "wb") as o:
         np.array([n], np.uint64).tofile(o)
         for x in (wi, wo, g):
             np.ascontiguousarray(x, np.float32).tofile(o)
-    r = subprocess.run([str(build), str(tmp / "f.bin"), str(tmp / "u.bin"), str(tmp / "o.bin")], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([str(build), str(tmp / "f.bin"), str(tmp / "u.bin"), str(tmp / "o.bin")] + (["mask"] if own_mask else []),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
+    assert f"MASK {file_mask(fields) if own_mask else 0}\n" in r.stdout, r.stdout
     out = np.fromfile(tmp / "o.bin", np.float32).reshape(3, n, 3)
     return out[0], out[1], out[2]

@@ -2,7 +2,9 @@
 // rgl::eval_dir_grad_spectral) and the product's image builder (csrc/merl_rgl.hip) compiled for the HOST, so that
 // tests/test_rgl_spectral_dir_grad_cpu.py can hold the gradient of eval on a spectral RGL material to its reference in a container
 // without a GPU.  No HIP runtime call is made.  Built by the test with hipcc.  Modelled on tests/rgl_dir_grad_host_harness.hip.
-//   usage: rgl_spectral_dir_grad_host_harness <fields.bin> <units.bin> <out.bin>
+//   usage: rgl_spectral_dir_grad_host_harness <fields.bin> <units.bin> <out.bin> [mask]
+//   mask: the per-lane function instantiated for the file's own bracket shape (MASK 1 / 3 / 5 / 15, what the single-material kernels
+//         run) instead of MASK 0 (the shape tested at run time, what the id kernel runs)
 //   fields.bin: int32 n_phi n_theta nx ny ndf_nx ndf_ny sigma_nx sigma_ny jacobian n_wavelengths, then phi_i theta_i ndf sigma vndf
 //               luminance spectra wavelengths (float32); every table [..][ny][nx]
 //   units.bin:  uint64 n, int32 W, int32 has_wl, then wi[n][3] wo[n][3] g[n][W] and (has_wl) wavelengths[n][W]
@@ -12,6 +14,8 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
 
 int main(int argc, char **argv)
 {
@@ -49,10 +53,22 @@ int main(int argc, char **argv)
     std::fclose(f);
     const mrl::rgl::GridMem grids{ r.phi, r.theta, r.wavelengths };
     float *gwl = &out[6 * n], *ev = &out[6 * n + rows];
+    const bool own = argc >= 5 && !std::strcmp(argv[4], "mask");
+    const int mask = own ? (1 | (r.n_phi > 1 ? 2 : 0) | (r.n_theta > 1 ? 4 : 0) | (r.n_phi > 1 && r.n_theta > 1 ? 8 : 0)) : 0;
+    auto unit = [&](auto m, size_t i, const float *wl_row) {
+        return mrl::rgl::eval_dir_grad_spectral<decltype(m)::value>(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2],
+                                                                    &g[(size_t)W * i], wl_row, W, has_wl ? gwl + (size_t)W * i : nullptr);
+    };
     for (size_t i = 0; i < n; ++i) {
         const float *wl_row = has_wl ? &wl[(size_t)W * i] : nullptr;
-        const mrl::rgl::RglDirGrad d = mrl::rgl::eval_dir_grad_spectral(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2],
-                                                                        &g[(size_t)W * i], wl_row, W, has_wl ? gwl + (size_t)W * i : nullptr);
+        mrl::rgl::RglDirGrad d;
+        switch (mask) {
+        case 1:  d = unit(std::integral_constant<int, 1>{}, i, wl_row); break;
+        case 3:  d = unit(std::integral_constant<int, 3>{}, i, wl_row); break;
+        case 5:  d = unit(std::integral_constant<int, 5>{}, i, wl_row); break;
+        case 15: d = unit(std::integral_constant<int, 15>{}, i, wl_row); break;
+        default: d = unit(std::integral_constant<int, 0>{}, i, wl_row); break;
+        }
         float pdf;
         for (int k = 0; k < 3; ++k) { out[3 * i + k] = d.wi[k]; out[3 * n + 3 * i + k] = d.wo[k]; }
         mrl::rgl::eval_pdf_spectral<true, false>(r, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], wl_row, W, ev + (size_t)W * i, pdf);
@@ -60,6 +76,6 @@ int main(int argc, char **argv)
     f = std::fopen(argv[3], "wb");
     if (!f || std::fwrite(out.data(), 4, out.size(), f) != out.size()) return 5;
     std::fclose(f);
-    std::printf("rgl spectral direction-gradient host harness ok: %llu units x %d wavelengths\n", n, W);
+    std::printf("rgl spectral direction-gradient host harness ok: %llu units x %d wavelengths, MASK %d\n", n, W, mask);
     return 0;
 }

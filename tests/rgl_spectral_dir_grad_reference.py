@@ -21,7 +21,7 @@ import torch
 
 from tests.nch_dir_grad_reference import dirty_g
 from tests.rgl_dir_grad_reference import (EXCUSED_CAP, HARMLESS, N_DEAD_FIXED, N_RANDOM, NEAR, REL, Arrays, _angles, _bracket, _cell,      # noqa: F401
-                                          _plain, _unit, check_side, contract, fixed_block, live_units)
+                                          _plain, _unit, check_side, contract, file_mask, fixed_block, live_units)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -224,6 +224,9 @@ FILES = {
     "aniso_red4": lambda: _synth(seed=56, n_phi=8, n_theta=4, res=(12, 10), reduction=4, n_wavelengths=4),
     "iso_rows": lambda: _synth(seed=58, n_phi=1, n_theta=6, res=12, sparse="rows", n_wavelengths=5),
     "iso_negative": lambda: _negative_band(_synth(seed=51, n_phi=1, n_theta=6, res=12, n_wavelengths=5)),
+    # the bracket shapes the kernels compile as MASK 3 (phi brackets only) and MASK 1 (one slice); appended: a file's index seeds its units
+    "phi_only": lambda: _synth(seed=60, n_phi=5, n_theta=1, res=(12, 10), n_wavelengths=4),
+    "theta1": lambda: _synth(seed=52, n_phi=1, n_theta=1, res=12, n_wavelengths=5),
 }
 FILE_NAMES = tuple(FILES)
 # the (file, W) cases: W = 4 on every file; on iso additionally 1, 7 and None (the file's own nodes)
@@ -308,8 +311,9 @@ def write_fields(path, f):
             np.ascontiguousarray(f[k], np.float32).tofile(o)
 
 
-def run_harness(build, tmp, fields, wi, wo, g, wl):
-    """the host-compiled per-lane function: (grad_wi [n, 3], grad_wo [n, 3], grad_wavelengths [n, W], eval [n, W]) f32"""
+def run_harness(build, tmp, fields, wi, wo, g, wl, own_mask=False):
+    """the host-compiled per-lane function: (grad_wi [n, 3], grad_wo [n, 3], grad_wavelengths [n, W], eval [n, W]) f32.  own_mask:
+    instantiated for the file's bracket shape (MASK = file_mask(fields), the single-material kernels' form) instead of MASK 0"""
     n, W = len(wi), g.shape[1]
     write_fields(tmp / "f.bin", fields)
     with open(tmp / "u.bin", "wb") as o:
@@ -317,7 +321,9 @@ def run_harness(build, tmp, fields, wi, wo, g, wl):
         np.array([W, 0 if wl is None else 1], np.int32).tofile(o)
         for x in (wi, wo, g) + (() if wl is None else (wl,)):
             np.ascontiguousarray(x, np.float32).tofile(o)
-    r = subprocess.run([str(build), str(tmp / "f.bin"), str(tmp / "u.bin"), str(tmp / "o.bin")], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([str(build), str(tmp / "f.bin"), str(tmp / "u.bin"), str(tmp / "o.bin")] + (["mask"] if own_mask else []),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
+    assert f"MASK {file_mask(fields) if own_mask else 0}\n" in r.stdout, r.stdout
     out = np.fromfile(tmp / "o.bin", np.float32)
     return out[:3 * n].reshape(n, 3), out[3 * n:6 * n].reshape(n, 3), out[6 * n:6 * n + n * W].reshape(n, W), out[6 * n + n * W:].reshape(n, W)

@@ -3,7 +3,9 @@
 // (csrc/merl_rgl.hip) compiled for the HOST, so that tests/test_rgl_values_grad_cpu.py can hold the gradient of eval in an RGL
 // material's values to its reference in a container without a GPU, and run the same code under the host sanitizers.  No HIP runtime
 // call is made.  Built by the test with hipcc.  Modelled on tests/rgl_dir_grad_host_harness.hip.
-//   usage: rgl_values_grad_host_harness grad <fields.bin> <units.bin> <out.bin>
+//   usage: rgl_values_grad_host_harness grad <fields.bin> <units.bin> <out.bin> [mask]
+//     mask: values_grad_unit instantiated for the file's own bracket shape (MASK 1 / 3 / 5 / 15, what the single-material kernels run)
+//           instead of MASK 0 (the shape tested at run time, what the id and the plain kernels run)
 //     fields.bin: as tests/rgl_dir_grad_host_harness.hip reads it
 //     units.bin:  uint64 n, then wi[n][3] wo[n][3] g[n][3] (float32), then one float64: what the two arrays hold before anything is added
 //     out.bin:    float64 [2][n_phi][n_theta][3][ny][nx]: the units through the gradient bricks and the fold; through values_texel
@@ -16,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -100,8 +103,20 @@ int main(int argc, char **argv)
     const size_t texels = sl * per * 3;
     std::vector<double> bricks(mrl::rgl::values_records(r.n_phi, r.n_theta, r.nx, r.ny) * (size_t)(16 * S), 0.0), out(2 * texels, start);
     size_t live = 0;
+    const bool own = argc >= 6 && !std::strcmp(argv[5], "mask");
+    const int mask = own ? (1 | (r.n_phi > 1 ? 2 : 0) | (r.n_theta > 1 ? 4 : 0) | (r.n_phi > 1 && r.n_theta > 1 ? 8 : 0)) : 0;
+    auto unit = [&](auto m, size_t i) {
+        return mrl::rgl::values_grad_unit<decltype(m)::value>(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], &g[3 * i]);
+    };
     for (size_t i = 0; i < n; ++i) {
-        const mrl::rgl::ValuesGradUnit u = mrl::rgl::values_grad_unit(r, grids, wi[3 * i], wi[3 * i + 1], wi[3 * i + 2], wo[3 * i], wo[3 * i + 1], wo[3 * i + 2], &g[3 * i]);
+        mrl::rgl::ValuesGradUnit u;
+        switch (mask) {
+        case 1:  u = unit(std::integral_constant<int, 1>{}, i); break;
+        case 3:  u = unit(std::integral_constant<int, 3>{}, i); break;
+        case 5:  u = unit(std::integral_constant<int, 5>{}, i); break;
+        case 15: u = unit(std::integral_constant<int, 15>{}, i); break;
+        default: u = unit(std::integral_constant<int, 0>{}, i); break;
+        }
         if (!u.live) continue;
         ++live;
         for (int slot = 0; slot < 12 * S; ++slot)
@@ -115,6 +130,6 @@ int main(int argc, char **argv)
     }
     fold(bricks, out.data(), r.n_phi, r.n_theta, r.nx, r.ny);
     if (const int rc = write_doubles(argv[4], out)) return rc;
-    std::printf("rgl values-gradient host harness ok: %llu units, %zu live\n", n, live);
+    std::printf("rgl values-gradient host harness ok: %llu units, %zu live, MASK %d\n", n, live, mask);
     return 0;
 }

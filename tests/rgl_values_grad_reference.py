@@ -97,9 +97,10 @@ def build_harness(tmp_path_factory, sanitize=False):
     return build
 
 
-def run_harness(build, tmp, fields, wi, wo, g, start=-0.0):
+def run_harness(build, tmp, fields, wi, wo, g, start=-0.0, own_mask=False):
     """(G_bricks, G_plain) f64 in the file's rgb layout: the units through values_grad_unit, the gradient bricks and fold_sources /
-    through values_texel, both added into arrays that held `start`"""
+    through values_texel, both added into arrays that held `start`.  own_mask: values_grad_unit instantiated for the file's bracket
+    shape (MASK = rref.file_mask(fields), the single-material brick kernels' form) instead of MASK 0"""
     n = len(wi)
     rref.write_fields(tmp / "f.bin", fields)
     with open(tmp / "u.bin", "wb") as o:
@@ -107,8 +108,10 @@ def run_harness(build, tmp, fields, wi, wo, g, start=-0.0):
         for x in (wi, wo, g):
             np.ascontiguousarray(x, np.float32).tofile(o)
         np.array([start], np.float64).tofile(o)
-    r = subprocess.run([str(build), "grad", str(tmp / "f.bin"), str(tmp / "u.bin"), str(tmp / "o.bin")], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([str(build), "grad", str(tmp / "f.bin"), str(tmp / "u.bin"), str(tmp / "o.bin")] + (["mask"] if own_mask else []),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
+    assert f"MASK {rref.file_mask(fields) if own_mask else 0}\n" in r.stdout, r.stdout
     shape = np.asarray(fields["rgb"]).shape
     out = np.fromfile(tmp / "o.bin", np.float64).reshape((2,) + shape)
     return out[0], out[1]

@@ -21,7 +21,7 @@ def _dev(*arrays):
     return [torch.from_numpy(np.array(a)).cuda() for a in arrays]
 
 
-@pytest.mark.parametrize("name,dtype", [("iso", "float64"), ("aniso", "float64"), ("iso_negative", "float32")])
+@pytest.mark.parametrize("name,dtype", [("iso", "float64"), ("aniso", "float64"), ("iso_negative", "float32"), ("phi_only", "float64")])
 def test_rgl_eval_is_differentiable_in_the_values(name, dtype):
     import torch
     from mitsuba_customization_amd import diff, host

@@ -37,7 +37,7 @@ def _units(c):
 
 
 @pytest.mark.parametrize("name,source", [("iso", "host"), ("iso", "device"), ("aniso", "host"), ("aniso", "device"), ("iso_phi2", "device"),
-                                         ("iso_theta1", "device"), ("aniso_red4", "host")])
+                                         ("iso_theta1", "device"), ("aniso_red4", "host"), ("phi_only", "host"), ("phi_only", "device")])
 def test_update_has_the_bits_of_a_fresh_upload_and_leaves_the_sampling_alone(name, source):
     import torch
     from mitsuba_customization_amd import host

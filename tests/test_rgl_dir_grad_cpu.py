@@ -5,10 +5,11 @@ oracle's rgl_eval_pdf_batch and the host-compiled product's eval), the per-lane 
 rgl_dir_grad_reference.FILES, the identities of the header are checked, the header and the library carry the calls, and the
 single-material kernels compile for gfx950 without scratch.
 
-Measured here (host build: the reciprocal and square-root seeds are the host's), 4,096 random units + the fixed block per file, 12
-files, both sides: worst |G - R| / S = 5.92e-8, the rounding of the f32 output (2^-24 sqrt(3) = 1.03e-7 at most); 0 random units
-excused on every file, 3 to 5 of the 20 live fixed ones; the reference's value agrees with the oracle's Float result to 4.9e-8 of the
-batch's largest value (the Float rounding of the result)."""
+Measured here (host build: the reciprocal and square-root seeds are the host's), 4,096 random units + the fixed block per file, 14
+files, both sides: worst |G - R| / S = 5.92e-8 (ggx_res32; phi_only 5.50e-8, phi_only_uneven 5.53e-8), the rounding of the f32
+output (2^-24 sqrt(3) = 1.03e-7 at most), with MASK 0 and with the file's own MASK, which have the same bits on every file; 0 random
+units excused on every file, 3 to 5 of the 20 live fixed ones; the reference's value agrees with the oracle's Float result to
+5.1e-8 of the batch's largest value (the Float rounding of the result)."""
 import os
 import re
 import shutil
@@ -74,6 +75,30 @@ def test_per_lane_function_on_the_host_meets_the_bar(name, tmp_path_factory):
     print(f"{name}: worst |G - R| / S = {worst:.2e} (so far {WORST['harness']:.2e})")
     assert (~d["alive"]).sum() == rref.N_DEAD_FIXED
     assert np.abs(Gi[held]).max() > 0 and np.abs(Go[held]).max() > 0
+
+
+@needs_hipcc
+@pytest.mark.parametrize("name", rref.FILE_NAMES)
+def test_per_lane_function_compiled_for_the_file_s_bracket_shape(name, tmp_path_factory):
+    """eval_dir_grad<MASK> with MASK the file's own shape (1 / 3 / 5 / 15: what k_rgl_dir_grad<*, false, MASK> runs) has the bits of
+    eval_dir_grad<0> (what the id kernel runs) — the header states the same operations in the same order either way — and meets the
+    bar itself."""
+    d = rref.case_data(name)
+    build = rref.build_harness(tmp_path_factory)
+    Gi, Go, _ = rref.run_harness(build, tmp_path_factory.mktemp("rgl_dir_grad_m0"), d["fields"], d["wi"], d["wo"], d["g"])
+    Mi, Mo, _ = rref.run_harness(build, tmp_path_factory.mktemp("rgl_dir_grad_m"), d["fields"], d["wi"], d["wo"], d["g"], own_mask=True)
+    worst = max(rref.check_side(Mi, d["Ji"], d["g"], d["alive"], d["excused"], name + " wi, own MASK"),
+                rref.check_side(Mo, d["Jo"], d["g"], d["alive"], d["excused"], name + " wo, own MASK"))
+    print(f"{name}: MASK {rref.file_mask(d['fields'])}, worst |G - R| / S = {worst:.2e}")
+    assert np.array_equal(bits(Mi), bits(Gi)) and np.array_equal(bits(Mo), bits(Go))
+    held = d["alive"] & ~d["excused"]
+    assert np.abs(Mi[held]).max() > 0 and np.abs(Mo[held]).max() > 0
+
+
+def test_the_files_cover_every_bracket_shape():
+    from tests import rgl_spectral_dir_grad_reference as sref
+    for ref in (rref, sref):
+        assert {ref.file_mask(ref.FILES[name]()) for name in ref.FILE_NAMES} == {1, 3, 5, 15}, ref.__name__
 
 
 @needs_hipcc

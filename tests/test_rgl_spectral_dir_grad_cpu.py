@@ -6,11 +6,12 @@ host and held to the bars on every case of rgl_spectral_dir_grad_reference.CASES
 3-node file that holds an RGB file's arrays returns the RGB function's bits, the header and the library carry the calls, and the
 kernels compile for gfx950 within the resources DESIGN.md §5q records.
 
-Measured here (host build: the reciprocal and square-root seeds are the host's), 4,096 random units + the fixed block per case, 10
-cases: worst |G - R| / S = 5.81e-8 on the directions, the rounding of the f32 output (2^-24 sqrt(3) = 1.03e-7 at most); worst
-grad_wavelengths error 5.82e-8 of its bar's term (iso_negative; 2.4e-8 elsewhere); 8 random units excused per case with
-wavelengths on a file of several nodes (the rows set to nodes), 0 otherwise, and 3 of the live fixed ones; the reference's value
-agrees with the oracle's Float result to 5.2e-8 of the batch's largest value."""
+Measured here (host build: the reciprocal and square-root seeds are the host's), 4,096 random units + the fixed block per case, 12
+cases on 9 files: worst |G - R| / S = 5.81e-8 on the directions (phi_only 5.70e-8, theta1 5.32e-8), the rounding of the f32 output
+(2^-24 sqrt(3) = 1.03e-7 at most); worst grad_wavelengths error 5.82e-8 of its bar's term (iso_negative; 2.5e-8 elsewhere: phi_only
+2.35e-8, theta1 2.15e-8), with MASK 0 and with the file's own MASK, which have the same bits in every case; 8 random units excused per
+case with wavelengths on a file of several nodes (the rows set to nodes), 0 otherwise, and 3 of the live fixed ones (5 on phi_only
+and theta1); the reference's value agrees with the oracle's Float result to 5.2e-8 of the batch's largest value."""
 import os
 import re
 import shutil
@@ -95,6 +96,25 @@ def test_per_lane_function_on_the_host_meets_the_bars(name, W, tmp_path_factory)
     print(f"{name} W={W}: worst |G - R| / S = {worst:.2e} (so far {WORST['dir']:.2e}); grad_wavelengths so far {WORST['wl']:.2e} of its term")
     assert (~d["alive"]).sum() == sref.N_DEAD_FIXED
     assert np.abs(Gi[held]).max() > 0 and np.abs(Go[held]).max() > 0
+
+
+@needs_hipcc
+@pytest.mark.parametrize("name,W", sref.CASES, ids=CASE_IDS)
+def test_per_lane_function_compiled_for_the_file_s_bracket_shape(name, W, tmp_path_factory):
+    """eval_dir_grad_spectral<MASK> with MASK the file's own shape (1 / 3 / 5 / 15: what k_rgl_spectral_dir_grad<*, false, MASK> runs)
+    has the bits of eval_dir_grad_spectral<0> (what the id kernel runs) in all three outputs, and meets the bars itself."""
+    d = sref.case_data(name, W)
+    build = sref.build_harness(tmp_path_factory)
+    args = (d["fields"], d["wi"], d["wo"], d["g"], d["wl"])
+    Gi, Go, Gl, _ = sref.run_harness(build, tmp_path_factory.mktemp("rgl_spectral_m0"), *args)
+    Mi, Mo, Ml, _ = sref.run_harness(build, tmp_path_factory.mktemp("rgl_spectral_m"), *args, own_mask=True)
+    worst = max(sref.check_side(Mi, d["Ji"], d["g"], d["alive"], d["excused"], f"{name} W={W} wi, own MASK"),
+                sref.check_side(Mo, d["Jo"], d["g"], d["alive"], d["excused"], f"{name} W={W} wo, own MASK"))
+    worst_wl = sref.check_wavelengths(Ml, d, f"{name} W={W} wavelengths, own MASK") if W is not None else 0.0
+    print(f"{name} W={W}: MASK {sref.file_mask(d['fields'])}, worst |G - R| / S = {worst:.2e}; grad_wavelengths {worst_wl:.2e} of its term")
+    assert np.array_equal(bits(Mi), bits(Gi)) and np.array_equal(bits(Mo), bits(Go)) and np.array_equal(bits(Ml), bits(Gl))
+    held = d["alive"] & ~d["excused"]
+    assert np.abs(Mi[held]).max() > 0 and np.abs(Mo[held]).max() > 0
 
 
 @needs_hipcc

@@ -3,10 +3,12 @@ against the library's symbols, the layout function, the per-lane function and th
 the host sanitizers) against the autograd reference of tests/rgl_values_grad_reference.py, the fold's record -> texel map, and the
 compiled kernels' assembly.
 
-Measured worst |G - R| / S per file, host-compiled per-lane function + fold and plain form alike (the bar is 1e-6):
-iso 2.2e-9, iso_nojac 4.9e-9, iso_theta1 6.5e-10, iso_phi2 1.6e-9, aniso 1.1e-8, aniso_red2 1.0e-9, aniso_red4 4.6e-9,
-aniso_uneven 5.8e-10, iso_rows 9.5e-11, iso_cols 3.7e-10, iso_negative 1.9e-9, ggx_res32 5.6e-8 — what eval's own f64 building
-blocks (v_rcp / v_rsq seeds with one Newton step, the atan polynomial) leave in the cell fractions next to torch's libm."""
+Measured on the host, 14 files, worst |G - R| / S per file, host-compiled per-lane function + fold and plain form alike, MASK 0 and
+the file's own MASK alike — the two have the same bits on every file — (the bar is 1e-6):
+iso 2.3e-9, iso_nojac 4.9e-9, iso_theta1 6.6e-10, iso_phi2 1.7e-9, aniso 1.2e-8, aniso_red2 1.1e-9, aniso_red4 4.7e-9,
+aniso_uneven 5.9e-10, iso_rows 9.5e-11, iso_cols 3.8e-10, iso_negative 1.9e-9, ggx_res32 5.7e-8, phi_only 2.9e-9, phi_only_uneven
+4.1e-9 — what eval's own f64 building blocks (v_rcp / v_rsq seeds with one Newton step, the atan polynomial) leave in the cell
+fractions next to torch's libm."""
 import os
 import re
 import subprocess
@@ -96,13 +98,31 @@ def test_per_lane_function_and_fold_against_the_reference(harness, tmp_path, nam
         assert np.abs(d[1] - c["S"]).max() > 0.0
 
 
-@pytest.mark.parametrize("name", ["iso", "aniso"])
+@pytest.mark.parametrize("name", vref.FILE_NAMES)
+def test_per_lane_function_compiled_for_the_file_s_bracket_shape(harness, tmp_path_factory, name):
+    """values_grad_unit<MASK> with MASK the file's own shape (1 / 3 / 5 / 15: what k_rgl_values_bricks<false, *, MASK> runs) yields
+    the bits of values_grad_unit<0> (the id and the plain kernels') — "the same operations either way" — in the gradient bricks after
+    the fold and in the plain form, and meets the bar itself."""
+    c = vref.case(name)
+    args = (c["fields"], c["wi"], c["wo"], c["g"], -0.0)
+    B0, P0 = vref.run_harness(harness, tmp_path_factory.mktemp("rgl_values_m0"), *args)
+    B, P = vref.run_harness(harness, tmp_path_factory.mktemp("rgl_values_m"), *args, own_mask=True)
+    vref.check(B, c, -0.0, f"{name} host bricks + fold, MASK {vref.rref.file_mask(c['fields'])}")
+    vref.check(P, c, -0.0, f"{name} host plain, MASK {vref.rref.file_mask(c['fields'])}")
+    assert np.array_equal(B.view(np.uint64), B0.view(np.uint64)) and np.array_equal(P.view(np.uint64), P0.view(np.uint64))
+    assert np.abs(B).max() > 0
+
+
+@pytest.mark.parametrize("name", ["iso", "aniso", "phi_only"])
 def test_per_lane_function_and_fold_under_the_host_sanitizers(tmp_path_factory, tmp_path, name):
     san = vref.build_harness(tmp_path_factory, sanitize=True)
     c = vref.case(name)
     G_bricks, G_plain = vref.run_harness(san, tmp_path, c["fields"], c["wi"], c["wo"], c["g"], 0.0)
     vref.check(G_bricks, c, 0.0, f"{name} host bricks + fold, ASan + UBSan")
     vref.check(G_plain, c, 0.0, f"{name} host plain, ASan + UBSan")
+    G_bricks, G_plain = vref.run_harness(san, tmp_path, c["fields"], c["wi"], c["wo"], c["g"], 0.0, own_mask=True)
+    vref.check(G_bricks, c, 0.0, f"{name} host bricks + fold, the file's own MASK, ASan + UBSan")
+    vref.check(G_plain, c, 0.0, f"{name} host plain, the file's own MASK, ASan + UBSan")
 
 
 @pytest.mark.parametrize("n_phi", [1, 2, 3])
