@@ -65,8 +65,8 @@ extern "C" {
  * material-id, queue and host-array forms return identical bits for the same unit, whatever n, the grid or the unit's position;
  * each output has the same bits whichever of the other outputs are requested.  Contraction is off and the FMAs are explicit in the
  * per-unit function.
- * Not offered: device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample, and the adjoint in
- * the file's values (fitting a file's spectra). */
+ * Not offered: device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and sample.  The adjoint in
+ * the file's values (fitting a file's spectra) is merl_hip_fit_rgl_spectral.h. */
 int mrl_rgl_grad_dir_spectral_batch(mrl_ctx *ctx, const float *wi, const float *wo,
                                     const float *wavelengths, int n_wavelengths, const float *grad_values,
                                     const int32_t *mat, int32_t single_id, size_t n,

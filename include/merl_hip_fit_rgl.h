@@ -52,7 +52,7 @@ extern "C" {
  * MRL_OPT_TABLE_GRAD_KERNEL selects the same four forms as for the table adjoint: 0 bricks, merged per wave when at least 4 lanes share
  * the first live lane's brick; 1 plain planar atomics (the measured baseline); 2 / 3 bricks never / always merged.  The sums are f64
  * atomics in no fixed order: two calls, and the four forms, agree to f64 rounding, not bit for bit.
- * Out of scope: spectral RGL files; device groups (mrl_group_*); the one-unit paths; plugin properties; rebuilding luminance;
+ * Out of scope: spectral RGL files here (their twin is merl_hip_fit_rgl_spectral.h); device groups (mrl_group_*); the one-unit paths; plugin properties; rebuilding luminance;
  * gradients in vndf / ndf / sigma; updates that change a file's shape. */
 int mrl_rgl_values_grad_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                               const int32_t *mat, int32_t single_id, size_t n,

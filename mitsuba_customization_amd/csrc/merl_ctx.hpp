@@ -11,8 +11,8 @@
 //                          tables: mrl_table_grad_batch_mat / mrl_table_grad_queue of merl_hip_fit_table.h): scatter kernels + calls
 //   merl_table_grad_nch.hip  the same adjoint on n-channel tables (mrl_table_grad_batch_nch / mrl_table_grad_queue_nch of
 //                          merl_hip_fit_nch.h): scatter kernels per (cell, channel group of 4) + calls
-//   merl_grad_scatter.hpp  what the scatter kernels of the three adjoints share (the two above and merl_rgl_values_grad.hip): the
-//                          wave's merge rule and its record-by-record scatter, fold_source, the f64 add.  Device code only
+//   merl_grad_scatter.hpp  what the scatter kernels of the four adjoints share (the two above, merl_rgl_values_grad.hip and
+//                          merl_rgl_spectral_values_grad.hip): the wave's merge rule and its record-by-record scatter, fold_source, the f64 add.  Device code only
 //   merl_grad_scatter.hip  grad_scatter_call, the host side of every adjoint call, and the kernel that clears their workspace
 //   merl_update.hip        new values for a resident material in place (include/merl_hip_update.h): table images through the upload's
 //                          build kernels, the row marginal on the device (reduction + finishing kernel), GGX parameters
@@ -27,6 +27,8 @@
 //   merl_rgl_dir_grad.hip  the same on RGB RGL materials (mrl_rgl_grad_dir_batch / _queue)
 //   merl_rgl_values_grad.hip  the adjoint of eval in the measured values of RGB RGL materials and their update in place
 //                          (include/merl_hip_fit_rgl.h): scatter, fold and write kernels + calls
+//   merl_rgl_spectral_values_grad.hip  the same adjoint in the spectra of spectral RGL materials and their update in place
+//                          (include/merl_hip_fit_rgl_spectral.h): scatter, fold and write kernels + calls
 #pragma once
 #include "../../include/merl_hip.h"
 
@@ -136,7 +138,8 @@ struct mrl_ctx {
     //   BUF_PART_WORK    mrl_partition_by_material: per-chunk count table + totals
     //   BUF_GRAD_BRICKS  the table-gradient calls: gradient bricks, one 256-B record per cell of every table of a call (merl_table_grad.hip),
     //                    per cell and channel group of 4 for n-channel tables (merl_table_grad_nch.hip), one 128 / 256 / 512-B record per
-    //                    (bracket, cell) of every RGL target (merl_rgl_values_grad.hip)
+    //                    (bracket, cell) of every RGL target (merl_rgl_values_grad.hip), n_wl x S x 32 B per (bracket, cell) of every
+    //                    spectral RGL target (merl_rgl_spectral_values_grad.hip)
     //   BUF_GGX_GRAD     mrl_ggx_grad_batch: one 256-B row of partial sums per block + the sums of a host-array call (merl_ggx_grad.hip)
     //   BUF_GGX_GRAD_MAT mrl_ggx_grad_batch_mat / mrl_ggx_grad_queue: one 256-B row per block and target + the sums of a host-array
     //                    call (merl_ggx_grad_mat.hip); its own buffer, so that what a captured graph points at never moves
@@ -252,7 +255,8 @@ struct DirGradFamily {
 int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f);
 
 // ---- merl_grad_scatter.hip ----
-// An adjoint-of-eval call (include/merl_hip.h mrl_table_grad_batch, merl_hip_fit_table.h, merl_hip_fit_nch.h, merl_hip_fit_rgl.h):
+// An adjoint-of-eval call (include/merl_hip.h mrl_table_grad_batch, merl_hip_fit_table.h, merl_hip_fit_nch.h, merl_hip_fit_rgl.h,
+// merl_hip_fit_rgl_spectral.h):
 // a gradient scattered into the measured data of the call's targets, whole arrays or a queue, and what its family supplies
 struct GradScatterCall {
     const float *wi, *wo, *g;
@@ -266,6 +270,11 @@ struct GradScatterCall {
     const int32_t *target_ids;
     int n_targets, max_targets;
     double *out;                                 // the targets' gradients end to end, added to
+    // one further per-unit input array (the spectral RGL adjoint: wavelengths); null: the call goes without it
+    const void *extra = nullptr;
+    size_t extra_bytes = 0;                      // of extra per unit
+    const char *extra_name = nullptr;
+    size_t cap_bytes = 0;                        // host arrays: > 0, chunks so small that the staging slot stays below it
 };
 struct GradScatterLayout {
     size_t brick_bytes;                          // of BUF_GRAD_BRICKS; 0: the launch adds straight into `out` — no reserve, no clear, no fold
@@ -277,6 +286,7 @@ struct GradScatterFamily {
     std::function<int(GradScatterLayout &)> layout;          // after every target passed: fills the family's own descriptors
     bool refuses_renormalise;                    // MRL_OPT_NEGATIVE = renormalise: MRL_ERR_INVALID
     // the accumulate kernel on m units at device-accessible arrays: addr[0..2] wi, wo, g and, where the call has one, addr[3] mat;
+    // where the call has an extra array it follows as the last address (addr[4] with mat, addr[3] without);
     // into the cleared bricks, or (brick_bytes = 0: bricks is null) into out
     std::function<hipError_t(char *const *addr, size_t m, double *bricks, double *out)> launch;
     std::function<hipError_t(const double *bricks, double *out)> fold;   // once per call, target by target; not called without bricks

@@ -1,5 +1,5 @@
-// merl_grad_scatter.hip — the host side the three adjoints of eval share (merl_table_grad.hip, merl_table_grad_nch.hip,
-// merl_rgl_values_grad.hip; DESIGN.md "What the adjoints share"): grad_scatter_call, and the clear of their workspace.
+// merl_grad_scatter.hip — the host side the four adjoints of eval share (merl_table_grad.hip, merl_table_grad_nch.hip,
+// merl_rgl_values_grad.hip, merl_rgl_spectral_values_grad.hip; DESIGN.md "What the adjoints share"): grad_scatter_call, and the clear of their workspace.
 //   k_grad_clear    zeros a call's gradient bricks (a kernel, not a memset: see there)
 #include "merl_ctx.hpp"
 
@@ -33,7 +33,7 @@ hipError_t launch_grad_clear(double *bricks, size_t bytes, int compute_units, hi
     return hipGetLastError();
 }
 
-// mrl_table_grad_batch* / mrl_table_grad_queue* / mrl_rgl_values_grad_* (GradScatterFamily); queued: over queue[0 .. min(*queue_count, n))
+// mrl_table_grad_batch* / mrl_table_grad_queue* / mrl_rgl_values_grad_* / mrl_rgl_spectral_values_grad_* (GradScatterFamily); queued: over queue[0 .. min(*queue_count, n))
 int grad_scatter_call(mrl_ctx *ctx, const GradScatterCall &c, const GradScatterFamily &f)
 {
     MRL_GUARD(ctx);
@@ -42,6 +42,7 @@ int grad_scatter_call(mrl_ctx *ctx, const GradScatterCall &c, const GradScatterF
     if (first_null(streams) || !c.out || !c.target_ids || (c.queued && (!c.queue || !c.queue_count)))
         return fail(ctx, MRL_ERR_INVALID, "null array argument");
     if (c.mat) streams.push_back({ (void *)c.mat, 4, false, "mat" });
+    if (c.extra) streams.push_back({ (void *)c.extra, c.extra_bytes, false, c.extra_name });
     if (c.n_targets < 1 || c.n_targets > c.max_targets) return fail(ctx, MRL_ERR_INVALID, "n_targets must be 1.." + std::to_string(c.max_targets));
     for (int k = 0; k < c.n_targets; ++k) {
         const int rc = f.check_target(c.target_ids[k]);
@@ -71,7 +72,7 @@ int grad_scatter_call(mrl_ctx *ctx, const GradScatterCall &c, const GradScatterF
         MRL_HIP(ctx, launch_grad_clear(bricks, lay.brick_bytes, ctx->compute_units, ctx->stream));
     }
     if (kind == 1) {
-        char *addr[4];
+        char *addr[5];
         for (size_t k = 0; k < streams.size(); ++k) addr[k] = (char *)streams[k].ptr;
         MRL_HIP(ctx, f.launch(addr, c.n, bricks, c.out));
         if (bricks) MRL_HIP(ctx, f.fold(bricks, c.out));
@@ -82,7 +83,7 @@ int grad_scatter_call(mrl_ctx *ctx, const GradScatterCall &c, const GradScatterF
     MRL_ALLOC(ctx, hipMalloc((void **)&d_out, lay.out_doubles * sizeof(double)));
     auto run = [&]() -> int {
         MRL_HIP(ctx, hipMemsetAsync(d_out, 0, lay.out_doubles * sizeof(double), ctx->stream));
-        const int rs = run_host_staged(ctx, streams, c.n, 0, [&](char *const *addr, size_t m) -> int {
+        const int rs = run_host_staged(ctx, streams, c.n, c.cap_bytes, [&](char *const *addr, size_t m) -> int {
             MRL_HIP(ctx, f.launch(addr, m, bricks, d_out));
             return MRL_OK;
         });

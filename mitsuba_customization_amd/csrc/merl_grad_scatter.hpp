@@ -1,5 +1,5 @@
-// merl_grad_scatter.hpp — what the scatter kernels of the three adjoints of eval share (merl_table_grad.hip, merl_table_grad_nch.hip,
-// merl_rgl_values_grad.hip; DESIGN.md "What the adjoints share"): the small helpers, and the protocol by which a wave adds its units'
+// merl_grad_scatter.hpp — what the scatter kernels of the four adjoints of eval share (merl_table_grad.hip, merl_table_grad_nch.hip,
+// merl_rgl_values_grad.hip, merl_rgl_spectral_values_grad.hip; DESIGN.md "What the adjoints share"): the small helpers, and the protocol by which a wave adds its units'
 // records.  Device code only.  A kernel parks, per lane, the key of its unit's record (s_key, -1 for a dead unit) and the unit's
 // factors in LDS, passes a barrier, and then the wave works through its units L lanes at a time: lane group `lane / L` carries one
 // record per wave-instruction, slot `lane % L` of it, so that a record is one contiguous run of f64 atomic adds.  What a slot's term

@@ -11,7 +11,8 @@ gradient in the material's own parameters is MerlHip.ggx_grad, in a table's texe
 same on a table material, rgl_eval on an RGL material, and eval serves every one of these kinds and batches that mix them.  table_eval_nch is MerlHip.eval_nch on n-channel
 tables (include/merl_hip_diff_nch.h, mrl_table_grad_dir_batch_nch): its values are [n, n_channels].
 rgl_spectral_eval is MerlHip.eval_spectral on spectral RGL materials (include/merl_hip_diff_rgl_spectral.h,
-mrl_rgl_grad_dir_spectral_batch): [n, W] values at per-unit wavelengths, differentiable in the wavelengths as well.
+mrl_rgl_grad_dir_spectral_batch): [n, W] values at per-unit wavelengths, differentiable in the wavelengths as well,
+and with values= in the files' spectra (include/merl_hip_fit_rgl_spectral.h).
 
 tables= and params= make the same calls differentiable in the MATERIAL as well: the table tensor(s) behind table
 materials, the 7 parameters behind GGX conductors.  Forward writes a tensor's current values into its resident material in place
@@ -99,10 +100,12 @@ class _SpectralEval(torch.autograd.Function):
     spectral eval of the host, backward_call(wi, wo, wavelengths, grad, want=) its gradient for a subset of ("wi", "wo",
     "wavelengths")"""
     @staticmethod
-    def forward(ctx, wi, wo, wavelengths, forward_call, backward_call):
+    def forward(ctx, wi, wo, wavelengths, forward_call, backward_call, material_call=None, *values):
         wi, wo, wavelengths = wi.contiguous(), wo.contiguous(), wavelengths.contiguous()
         ctx.save_for_backward(wi, wo, wavelengths)
         ctx.backward_call = backward_call
+        ctx.material_call = material_call                       # (wi, wo, wavelengths, grad, needed) -> the gradients in `values`
+        ctx.n_values = len(values)
         return forward_call(wi, wo, wavelengths)
 
     @staticmethod
@@ -110,11 +113,48 @@ class _SpectralEval(torch.autograd.Function):
         wi, wo, wavelengths = ctx.saved_tensors
         # only what the graph asks for: the other output pointers are NULL and those gradients are neither computed nor written
         want = tuple(name for name, needed in zip(("wi", "wo", "wavelengths"), ctx.needs_input_grad[:3]) if needed)
+        g = grad_values.contiguous()
         grads = {}
         if want:
-            out = ctx.backward_call(wi, wo, wavelengths, grad_values.contiguous(), want=want)
+            out = ctx.backward_call(wi, wo, wavelengths, g, want=want)
             grads = dict(zip(want, (out,) if len(want) == 1 else out))
-        return (grads.get("wi"), grads.get("wo"), grads.get("wavelengths"), None, None)
+        needed = [i for i, need in enumerate(ctx.needs_input_grad[6:]) if need]
+        in_values = ctx.material_call(wi, wo, wavelengths, g, needed) if needed else [None] * ctx.n_values
+        return (grads.get("wi"), grads.get("wo"), grads.get("wavelengths"), None, None, None, *in_values)
+
+
+class _SpectralValues:
+    """The spectra tensors behind the spectral RGL materials of one rgl_spectral_eval call: {material id: tensor}.  refresh() makes
+    every material hold its tensor's current values (the record of _Materials.refresh, shared with it); gradients() is
+    _SpectralEval's material_call: one MerlHip.rgl_spectral_values_grad launch for all tensors that need a gradient."""
+
+    def __init__(self, gpu, mat, material, values):
+        self.gpu, self.mat, self.material = gpu, mat, material
+        self.entries = [(int(k), t) for k, t in (values.items() if isinstance(values, dict) else [(material, values)])]
+        for _, t in self.entries:
+            if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.float64):
+                raise ValueError("values=: torch.float32 or torch.float64 tensors [n_phi, n_theta, n_wl, ny, nx]")
+
+    @property
+    def values(self):
+        return tuple(t for _, t in self.entries)
+
+    def refresh(self):
+        record = self.gpu.__dict__.setdefault("_resident", {})
+        self.gpu.use_torch_stream()                             # the updates run on the stream the eval behind them will run on
+        for mid, t in self.entries:
+            seen = record.get(mid)
+            if seen is not None and seen[0]() is t and seen[1:] == (t.data_ptr(), t._version):
+                continue
+            self.gpu.update_rgl_spectral_values(mid, t.detach().to(torch.float32).contiguous())   # rounded once, on the device
+            record[mid] = (weakref.ref(t), t.data_ptr(), t._version)
+
+    def gradients(self, wi, wo, wavelengths, g, needed):
+        out = [None] * len(self.entries)
+        grads = self.gpu.rgl_spectral_values_grad(wi, wo, wavelengths, g, [self.entries[i][0] for i in needed], mat=self.mat, material=self.material)
+        for i, grad in zip(needed, grads):
+            out[i] = grad.to(self.entries[i][1].dtype)
+        return out
 
 
 class _Materials:
@@ -245,21 +285,32 @@ def rgl_eval(ctx, wi, wo, mat=None, material: int = 0, values=None):
                   mat, material, values=values)
 
 
-def rgl_spectral_eval(ctx, wi, wo, wavelengths, mat=None, material: int = 0):
+def rgl_spectral_eval(ctx, wi, wo, wavelengths, mat=None, material: int = 0, values=None):
     """MerlHip.eval_spectral(wi, wo, wavelengths, material) — with mat=, eval_spectral_mat — of the context `ctx`: [n, W] values at the
     per-unit wavelengths [n, W] (float32 device tensor), differentiable in wi, wo AND the wavelengths.  The materials must be
     spectral RGL materials (upload_rgl of a file with "spectra"): the backward pass of a single material of another kind raises
     MRL_ERR_MATERIAL, and with mat= a unit whose id names no live spectral RGL material receives zero gradients.  Backward is one
     MerlHip.rgl_grad_dir_spectral call for what the graph needs (include/merl_hip_diff_rgl_spectral.h): the exact gradient of the
     piecewise function in the cells and the wavelength bracket eval selects; d value / d wavelength is piecewise constant, 0 outside
-    the file's nodes and where the value is clamped.  The file's values are not differentiable."""
+    the file's nodes and where the value is clamped.
+    values=: a device tensor [n_phi, n_theta, n_wl, ny, nx] (f32 or f64) for the single material, or {id: tensor} with mat=: the call
+    is differentiable in the files' spectra too (include/merl_hip_fit_rgl_spectral.h).  Forward writes a tensor into
+    its resident material with MerlHip.update_rgl_spectral_values — in place, from device memory, rounded to float — only when
+    (data_ptr, _version) differs from what that material last received; backward is one MerlHip.rgl_spectral_values_grad launch for
+    all tensors that need a gradient, beside the direction and wavelength call, cast to each tensor's dtype.  vndf, ndf, sigma,
+    luminance, the grids and the wavelength nodes are not differentiable."""
     if wavelengths is None:
         raise ValueError("rgl_spectral_eval: per-unit wavelengths [n, W] (the file's own nodes are no differentiable input)")
     if mat is None:
         forward = lambda a, b, wl: ctx.eval_spectral(a, b, wl, material)
     else:
         forward = lambda a, b, wl: ctx.eval_spectral_mat(a, b, wl, mat)
-    return _SpectralEval.apply(wi, wo, wavelengths, forward, partial(ctx.rgl_grad_dir_spectral, mat=mat, material=material))
+    backward = partial(ctx.rgl_grad_dir_spectral, mat=mat, material=material)
+    if values is None:
+        return _SpectralEval.apply(wi, wo, wavelengths, forward, backward)
+    m = _SpectralValues(ctx, mat, material, values)
+    m.refresh()
+    return _SpectralEval.apply(wi, wo, wavelengths, forward, backward, m.gradients, *m.values)
 
 
 def eval(ctx, wi, wo, mat=None, material: int = 0, tables=None, params=None, values=None):

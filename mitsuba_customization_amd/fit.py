@@ -8,7 +8,9 @@ A GGX conductor (alpha, eta[3], k[3]): Levenberg-Marquardt on sum w (eval - y)^2
 (fit_ggx; the loop itself, lm_ggx, takes eval and gradient as callables).  fit_ggx_mat / lm_ggx_mat fit several conductors at once
 from one interleaved set with a material index per unit, on MerlHip.ggx_grad_mat: one eval and one gradient launch per iteration.
 The measured values of an RGB RGL file (fit_rgl_values): CGLS over R >= 0 on MerlHip.eval and MerlHip.rgl_values_grad, the other
-fields of the file fixed; every iterate is written into the resident material with MerlHip.update_rgl_values.
+fields of the file fixed; every iterate is written into the resident material with MerlHip.update_rgl_values.  The spectra of a
+spectral RGL file from samples at per-unit wavelengths (fit_rgl_spectral_values): the same loop on MerlHip.eval_spectral,
+MerlHip.rgl_spectral_values_grad and MerlHip.update_rgl_spectral_values.
 
 The context's lookup / node / cosine options define A.  fit_table makes iterates resident that have negative entries, so A is linear
 only with host.OPT_NEGATIVE at keep (1), set before the context's first table is uploaded.
@@ -103,6 +105,50 @@ def fit_table(ctx, dims, wi, wo, rgb, iters, param=None, scale=(1.0, 1.0, 1.0)):
         ctx.release_material(shape_mid)
 
 
+def _cgls_nonneg(zeros, shape, A, At, y, start, iters, name):
+    """the loop of fit_rgl_values / fit_rgl_spectral_values: CGLS inside the face of x >= 0 the iterate lies in.  Returns (x, residuals)"""
+    if start is None:
+        one = zeros() + 1.0
+        a1 = A(one)
+        x = one * max(_dot(a1, y) / max(_dot(a1, a1), 1e-300), 0.0)
+    else:
+        x = _f64(start).reshape(shape) + zeros()
+        if float(x.min()) < 0.0:
+            raise ValueError(f"{name}: the start must lie in R >= 0")
+    r = y - A(x)
+    residuals = [_dot(r, r) ** 0.5]
+    p, gamma, free = None, 0.0, None
+    for _ in range(iters):
+        s = At(r)
+        now_free = (x > 0) | (s > 0)
+        s = s * now_free
+        g_new = _dot(s, s)
+        restart = p is None or gamma == 0.0 or not bool((now_free == free).all())
+        p = s if restart else s + (g_new / gamma) * p
+        gamma, free = g_new, now_free
+        q = A(p)
+        qq = _dot(q, q)
+        if g_new == 0.0 or qq == 0.0:
+            residuals.append(residuals[-1])
+            continue
+        alpha = _dot(r, q) / qq                                     # the minimiser along p (CGLS: gamma / qq while p is conjugate)
+        shrinking = p < 0
+        if bool(shrinking.any()):                                   # the longest step that stays in R >= 0
+            room = float((x[shrinking] / -p[shrinking]).min())
+            if room < alpha:
+                alpha, p_next = room, None
+            else:
+                p_next = p
+        else:
+            p_next = p
+        x = x + alpha * p
+        x = x * (x > 0)                                             # (a value that reaches 0 is 0, not a rounding below it)
+        r = r - alpha * q
+        p = p_next
+        residuals.append(_dot(r, r) ** 0.5)
+    return x, residuals
+
+
 # ---- the measured values of an RGB RGL material (MerlHip.eval is A, MerlHip.rgl_values_grad is A^T; DESIGN.md §5r) ----
 def fit_rgl_values(ctx, mid, wi, wo, rgb, iters, start=None):
     """min |eval(R) - y|^2 over R >= 0 in the measured values R of the resident RGB RGL material `mid`, its other fields (vndf, ndf,
@@ -136,46 +182,43 @@ def fit_rgl_values(ctx, mid, wi, wo, rgb, iters, start=None):
     def At(r):
         return ctx.rgl_values_grad(wi, wo, _f32(r), [mid], material=mid)[0]
 
-    if start is None:
-        one = zeros() + 1.0
-        a1 = A(one)
-        x = one * max(_dot(a1, y) / max(_dot(a1, a1), 1e-300), 0.0)
-    else:
-        x = _f64(start).reshape(shape) + zeros()
-        if float(x.min()) < 0.0:
-            raise ValueError("fit_rgl_values: the start must lie in R >= 0")
-    r = y - A(x)
-    residuals = [_dot(r, r) ** 0.5]
-    p, gamma, free = None, 0.0, None
-    for _ in range(iters):
-        s = At(r)
-        now_free = (x > 0) | (s > 0)
-        s = s * now_free
-        g_new = _dot(s, s)
-        restart = p is None or gamma == 0.0 or not bool((now_free == free).all())
-        p = s if restart else s + (g_new / gamma) * p
-        gamma, free = g_new, now_free
-        q = A(p)
-        qq = _dot(q, q)
-        if g_new == 0.0 or qq == 0.0:
-            residuals.append(residuals[-1])
-            continue
-        alpha = _dot(r, q) / qq                                     # the minimiser along p (CGLS: gamma / qq while p is conjugate)
-        shrinking = p < 0
-        if bool(shrinking.any()):                                   # the longest step that stays in R >= 0
-            room = float((x[shrinking] / -p[shrinking]).min())
-            if room < alpha:
-                alpha, p_next = room, None
-            else:
-                p_next = p
-        else:
-            p_next = p
-        x = x + alpha * p
-        x = x * (x > 0)                                             # (a value that reaches 0 is 0, not a rounding below it)
-        r = r - alpha * q
-        p = p_next
-        residuals.append(_dot(r, r) ** 0.5)
+    x, residuals = _cgls_nonneg(zeros, shape, A, At, y, start, iters, "fit_rgl_values")
     ctx.update_rgl_values(mid, _f32(x))
+    return x, residuals
+
+
+# ---- the spectra of a spectral RGL material (MerlHip.eval_spectral is A, MerlHip.rgl_spectral_values_grad is A^T) ----
+def fit_rgl_spectral_values(ctx, mid, wi, wo, wavelengths, values, iters, start=None):
+    """min |eval_spectral(R) - y|^2 over R >= 0 in the spectra R of the resident spectral RGL material `mid`, its other fields (vndf,
+    ndf, sigma, luminance, the grids, the wavelength nodes) fixed: fit_rgl_values on MerlHip.eval_spectral (A),
+    MerlHip.rgl_spectral_values_grad (A^T) and MerlHip.update_rgl_spectral_values.  wavelengths: [n, W] per-unit wavelengths (hero
+    wavelengths), values: the measurements y [n, W].  Every array the loop evaluates is written into `mid` in place, and `mid` holds
+    the result when the call returns.  start: spectra [n_phi, n_theta, n_wl, ny, nx] >= 0, or None for the constant file that fits
+    best.  Returns (R f64 like the file's spectra, [|eval_spectral(R_k) - y| for k = 0 .. iters])."""
+    shape = ctx.rgl_spectral_values_shape(mid)
+    tensor = host._is_tensor(wi)
+    y = _f64(values)
+
+    def zeros():
+        if tensor:
+            import torch
+            return torch.zeros(shape, dtype=torch.float64, device=wi.device)
+        return np.zeros(shape, np.float64)
+
+    def A(v):                                                       # linear for every sign of v
+        pos, neg = v * (v > 0), -v * (v < 0)
+        ctx.update_rgl_spectral_values(mid, _f32(pos))
+        out = _f64(ctx.eval_spectral(wi, wo, wavelengths, mid))
+        if float(neg.max()) > 0.0:
+            ctx.update_rgl_spectral_values(mid, _f32(neg))
+            out = out - _f64(ctx.eval_spectral(wi, wo, wavelengths, mid))
+        return out
+
+    def At(r):
+        return ctx.rgl_spectral_values_grad(wi, wo, wavelengths, _f32(r), [mid], material=mid)[0]
+
+    x, residuals = _cgls_nonneg(zeros, shape, A, At, y, start, iters, "fit_rgl_spectral_values")
+    ctx.update_rgl_spectral_values(mid, _f32(x))
     return x, residuals
 
 

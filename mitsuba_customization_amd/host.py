@@ -93,6 +93,11 @@ UPDATE_KEEP_SAMPLING = 1            # MRL_UPDATE_KEEP_SAMPLING
 FIT_RGL_ABI_SYMBOLS = ("mrl_rgl_values_grad_batch", "mrl_rgl_values_grad_queue", "mrl_rgl_values_shape", "mrl_rgl_values_grad_layout",
                        "mrl_material_update_rgl_values")
 RGL_GRAD_MAX_TARGETS = 16           # MRL_RGL_GRAD_MAX_TARGETS
+# every symbol include/merl_hip_fit_rgl_spectral.h declares: the adjoint of eval_spectral in the spectra of spectral RGL materials, and
+# their update in place
+FIT_RGL_SPECTRAL_ABI_SYMBOLS = ("mrl_rgl_spectral_values_grad_batch", "mrl_rgl_spectral_values_grad_queue", "mrl_rgl_spectral_values_shape",
+                                "mrl_rgl_spectral_values_grad_layout", "mrl_material_update_rgl_spectral_values")
+RGL_SPECTRAL_GRAD_MAX_TARGETS = 16  # MRL_RGL_SPECTRAL_GRAD_MAX_TARGETS
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 0, 1, 2
 ERR_COMM = -9
 
@@ -263,6 +268,14 @@ _RGL_TARGETS = ("target_ids", "n_targets", "grad_values")
 _CALLS["batch", "rgl_values_grad"] = ("mrl_rgl_values_grad_batch", _FAMILIES["batch"][1] + _RGL_TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
 _CALLS["queue", "rgl_values_grad"] = ("mrl_rgl_values_grad_queue", _FAMILIES["queue"][1] + _RGL_TARGETS, (_WI, _WO, ("grad_rgb", 3)), ())
 _CALLS["material", "update_rgl_values"] = ("mrl_material_update_rgl_values", ("id", "rgb", "flags"), (), ())
+# the same on spectral RGL materials (include/merl_hip_fit_rgl_spectral.h): wavelengths and their number lead the middle parameters, as in
+# the spectral eval calls, and grad_values [n, n_wavelengths] follows them as one more stream
+_RGL_SPECTRAL_TARGETS = ("target_ids", "n_targets", "grad_spectra")
+_CALLS["batch", "rgl_spectral_values_grad"] = ("mrl_rgl_spectral_values_grad_batch",
+                                               ("wavelengths", "n_wavelengths", "grad_values") + _FAMILIES["batch"][1] + _RGL_SPECTRAL_TARGETS, (_WI, _WO), ())
+_CALLS["queue", "rgl_spectral_values_grad"] = ("mrl_rgl_spectral_values_grad_queue",
+                                               ("wavelengths", "n_wavelengths", "grad_values") + _FAMILIES["queue"][1] + _RGL_SPECTRAL_TARGETS, (_WI, _WO), ())
+_CALLS["material", "update_rgl_spectral_values"] = ("mrl_material_update_rgl_spectral_values", ("id", "spectra", "flags"), (), ())
 
 
 _lib = None
@@ -319,6 +332,8 @@ def load_library(path: Optional[str] = None):
     L.mrl_table_grad_layout_nch.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     L.mrl_rgl_values_shape.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.mrl_rgl_values_grad_layout.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_size_t)]
+    L.mrl_rgl_spectral_values_shape.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.mrl_rgl_spectral_values_grad_layout.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_size_t)]
     L.mrl_ggx_grad_batch.argtypes = [vp, fp, fp, fp, fp, C.c_int32, C.c_size_t, vp, vp]
     L.mrl_ggx_grad_dir_batch.argtypes = [vp, fp, fp, fp, vp, C.c_int32, C.c_size_t, fp, fp]
     L.mrl_ggx_grad_dir_queue.argtypes = [vp, fp, fp, fp, vp, C.c_int32, vp, vp, C.c_size_t, fp, fp]
@@ -527,6 +542,22 @@ def rgl_values_grad_layout(shapes) -> list:
     if load_library().mrl_rgl_values_grad_layout(flat, len(shapes), offsets) != 0:
         raise ValueError(f"rgl_values_grad_layout: 1..{RGL_GRAD_MAX_TARGETS} targets of shape (n_phi >= 1, n_theta >= 1, 3, ny >= 2, nx >= 2) "
                          "and at most 2^31 - 1 workspace records in all")
+    return list(offsets)
+
+
+def rgl_spectral_values_grad_layout(shapes) -> list:
+    """mrl_rgl_spectral_values_grad_layout: where each target's slice of the rgl_spectral_values_grad / rgl_spectral_values_grad_queue
+    buffer starts, in f64 values; shapes: (n_phi, n_theta, n_wl, ny, nx) per target, as MerlHip.rgl_spectral_values_shape() reports
+    them.  Returns n_targets + 1 offsets, the last one the buffer's size.  ValueError for what the calls refuse
+    (include/merl_hip_fit_rgl_spectral.h)."""
+    shapes = [tuple(sh) for sh in shapes]
+    if any(len(sh) != 5 or any(not -2**31 <= int(d) < 2**31 for d in sh) for sh in shapes):
+        raise ValueError("rgl_spectral_values_grad_layout: every target has five dims that fit an int")
+    flat = (C.c_int * max(5 * len(shapes), 1))(*[int(d) for sh in shapes for d in sh])
+    offsets = (C.c_size_t * (len(shapes) + 1))()
+    if load_library().mrl_rgl_spectral_values_grad_layout(flat, len(shapes), offsets) != 0:
+        raise ValueError(f"rgl_spectral_values_grad_layout: 1..{RGL_SPECTRAL_GRAD_MAX_TARGETS} targets of shape (n_phi >= 1, n_theta >= 1, "
+                         "1 <= n_wl <= 4096, ny >= 2, nx >= 2) and at most 2^31 - 1 (workspace record, node) pairs in all")
     return list(offsets)
 
 
@@ -823,6 +854,28 @@ class MerlHip:
         self._forget_resident(mid)
         _material_call(self, "update_rgl_values", id=int(mid), rgb=ptr, flags=0)
 
+    def rgl_spectral_values_shape(self, mid: int) -> tuple:
+        """(n_phi, n_theta, n_wl, ny, nx) of the spectra array of the spectral RGL material `mid` (mrl_rgl_spectral_values_shape)."""
+        shape = (C.c_int * 5)()
+        self._check(self._lib.mrl_rgl_spectral_values_shape(self._ctx, int(mid), shape), "mrl_rgl_spectral_values_shape")
+        return tuple(int(d) for d in shape)
+
+    def update_rgl_spectral_values(self, mid: int, spectra):
+        """New spectra for the resident spectral RGL material `mid` (mrl_material_update_rgl_spectral_values): same id, same addresses;
+        vndf, ndf, sigma, luminance, the grids and the wavelength nodes stay as they are (pdf and sampled directions keep their bits).
+        spectra: f32, contiguous, [n_phi, n_theta, n_wl, ny, nx] as uploaded — a numpy array (checked for non-finite values, staged) or
+        a device tensor (read in place on torch's current stream: no copy, no synchronisation; finite values are the caller's
+        responsibility).  ValueError for a wrong dtype, layout or shape."""
+        shape = self.rgl_spectral_values_shape(mid)
+        if _is_tensor(spectra) and not spectra.is_cuda:
+            raise ValueError("spectra: torch tensors must live on the GPU (pass a numpy array for host data)")
+        if tuple(spectra.shape) != shape:
+            raise ValueError(f"spectra: shape {tuple(spectra.shape)}, the material was uploaded from {shape}")
+        ptr = _addr(spectra, np.float32, None, None, "spectra")
+        self._prep(spectra)
+        self._forget_resident(mid)
+        _material_call(self, "update_rgl_spectral_values", id=int(mid), spectra=ptr, flags=0)
+
     def _forget_resident(self, mid: int):
         """diff.py records on this object which tensor a material last received (tables= / params=); whoever changes or releases the
         material drops that record"""
@@ -1044,6 +1097,64 @@ class MerlHip:
         """rgl_values_grad() of the slots queue[0 .. min(count, capacity)) (mrl_rgl_values_grad_queue); a slot listed twice adds twice.
         GPU tensors only."""
         return self._rgl_values_grad("queue", wi, wo, grad_rgb, targets, mat, material, out, queue=(queue, count, capacity))
+
+    def _rgl_spectral_values_grad(self, family, wi, wo, wavelengths, grad_values, targets, mat, material, n_wavelengths, out,
+                                  queue=(None, None, None)):
+        """One call of include/merl_hip_fit_rgl_spectral.h through its row of _CALLS: _rgl_values_grad for spectral targets.  Returns
+        the targets' gradients [n_phi, n_theta, n_wl, ny, nx] as views of one f64 buffer that holds them end to end."""
+        targets = [int(t) for t in targets]
+        symbol = _CALLS[family, "rgl_spectral_values_grad"][0]
+        if not 1 <= len(targets) <= RGL_SPECTRAL_GRAD_MAX_TARGETS:
+            raise MerlHipError(ERR_INVALID, symbol, f"1..{RGL_SPECTRAL_GRAD_MAX_TARGETS} targets")
+        shapes = [self.rgl_spectral_values_shape(t) for t in targets]       # ERR_MATERIAL for a target that is no live spectral RGL material
+        offsets = rgl_spectral_values_grad_layout(shapes)
+        total = offsets[-1]
+        n = int(wi.shape[0])
+        if wavelengths is None:
+            if n_wavelengths is None:
+                raise ValueError("n_wavelengths: needed without a wavelength array (the number of the file's nodes)")
+            W = int(n_wavelengths)
+        else:
+            W = int(wavelengths.shape[1])
+            if n_wavelengths is not None and int(n_wavelengths) != W:
+                raise ValueError(f"n_wavelengths = {n_wavelengths}, but wavelengths has {W} columns")
+        if _is_tensor(wi):
+            import torch
+            if out is None:
+                out = torch.zeros((total,), dtype=torch.float64, device=wi.device)
+            if not _is_tensor(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != total:
+                raise ValueError(f"out: need a contiguous torch.float64 tensor of {total} values (the targets end to end)")
+            ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.zeros((total,), dtype=np.float64)
+            if not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.size != total:
+                raise ValueError(f"out: need a C-contiguous numpy float64 array of {total} values (the targets end to end)")
+            ptr = out.ctypes.data
+        cols = max(W, 1)
+        more = {"target_ids": (C.c_int32 * len(targets))(*targets), "n_targets": len(targets), "grad_spectra": ptr,
+                "wavelengths": _addr(wavelengths, np.float32, cols, n, "wavelengths"), "n_wavelengths": W,
+                "grad_values": _addr(grad_values, np.float32, cols, n, "grad_values")}
+        _stream_call(self, family, "rgl_spectral_values_grad", (wi, wo), None, cols, None, mat, material, *queue, more=more)
+        flat = out.reshape(-1)
+        return tuple(flat[a:b].reshape(sh) for a, b, sh in zip(offsets, offsets[1:], shapes))
+
+    def rgl_spectral_values_grad(self, wi, wo, wavelengths, grad_values, targets, mat=None, material: int = 0,
+                                 n_wavelengths: Optional[int] = None, out=None):
+        """G_k += (d eval_spectral / d R_k)^T grad_values for every spectral RGL material in `targets` in one launch
+        (mrl_rgl_spectral_values_grad_batch, include/merl_hip_fit_rgl_spectral.h): the adjoint of eval_spectral in a file's spectra.
+        wavelengths: [n, W] f32, or None for the file's own nodes (n_wavelengths = their number; without mat=); grad_values [n, W] f32.
+        A unit adds into the target its material id names — mat[i], or `material` for all units — and into nothing if that id is not
+        among the targets.  Returns a tuple of f64 arrays [n_phi, n_theta, n_wl, ny, nx], views of one buffer that holds the targets
+        end to end; numpy in -> numpy out, device tensors in -> device tensors out; out= (that one buffer) is accumulated into."""
+        return self._rgl_spectral_values_grad("batch", wi, wo, wavelengths, grad_values, targets, mat, material, n_wavelengths, out)
+
+    def rgl_spectral_values_grad_queue(self, wi, wo, wavelengths, grad_values, queue, count, targets, mat=None, material: int = 0, capacity=None,
+                                       n_wavelengths: Optional[int] = None, out=None):
+        """rgl_spectral_values_grad() of the slots queue[0 .. min(count, capacity)) (mrl_rgl_spectral_values_grad_queue); a slot listed
+        twice adds twice.  GPU tensors only; capturable in a HIP graph after one call outside the capture."""
+        return self._rgl_spectral_values_grad("queue", wi, wo, wavelengths, grad_values, targets, mat, material, n_wavelengths, out,
+                                              queue=(queue, count, capacity))
 
     def ggx_grad(self, wi, wo, grad_rgb, material: int, curvature=None, normal: bool = False, out=None):
         """The parameter gradient of eval on a GGX material (mrl_ggx_grad_batch), parameters in the order (alpha, eta[3], k[3]):
