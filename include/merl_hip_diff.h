@@ -40,8 +40,8 @@ extern "C" {
  * Not offered here: RGB table materials have the same pair of calls in merl_hip_diff_table.h (mrl_table_grad_dir_batch / _queue),
  * n-channel tables in merl_hip_diff_nch.h (mrl_table_grad_dir_batch_nch / _queue_nch).
  * RGB RGL materials in merl_hip_diff_rgl.h (mrl_rgl_grad_dir_batch / _queue).
- * Not offered: spectral RGL materials, device groups (mrl_group_*), the one-unit paths, second derivatives, gradients of pdf and
- * sample. */
+ * Not offered: spectral RGL materials, device groups (mrl_group_*), the one-unit paths, second derivatives.
+ * The gradients of pdf and sample on GGX conductors live in merl_hip_diff_sample.h (mrl_ggx_pdf_grad_batch, mrl_ggx_sample_grad_batch). */
 int mrl_ggx_grad_dir_batch(mrl_ctx *ctx, const float *wi, const float *wo, const float *grad_rgb,
                            const int32_t *mat, int32_t single_id, size_t n,
                            float *grad_wi, float *grad_wo);

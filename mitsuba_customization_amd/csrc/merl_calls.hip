@@ -266,7 +266,7 @@ int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f)
     MRL_GUARD(ctx);
     if (c.n == 0) return MRL_OK;
     if (c.queued && (!c.queue || !c.queue_count)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
-    StreamList streams = { { (void *)c.wi, 12, false, "wi" }, { (void *)c.wo, 12, false, "wo" }, { (void *)c.g, f.g_bytes, false, f.g_name } };
+    StreamList streams = { { (void *)c.wi, 12, false, "wi" }, { (void *)c.wo, f.second_bytes, false, f.second_name }, { (void *)c.g, f.g_bytes, false, f.g_name } };
     for (const DirGradExtra &x : c.extra) if (x.required) streams.push_back({ x.ptr, x.unit_bytes, x.out, x.name });
     if (first_null(streams)) return fail(ctx, MRL_ERR_INVALID, "null array argument");
     streams.resize(3);

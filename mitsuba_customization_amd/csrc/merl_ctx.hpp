@@ -22,6 +22,7 @@
 //   merl_dir_grad.hpp      what the direction-gradient kernels share: the grid-stride loop with its masked stores, the record a
 //                          material id names, the PER_LANE / INDEXED dispatch; their one host call is grad_dir_call of merl_calls.hip
 //   merl_ggx_dir_grad.hip  the direction gradient of eval on GGX conductors (mrl_ggx_grad_dir_batch / _queue): streaming kernel + calls
+//   merl_ggx_sample_grad.hip  the gradients of pdf and sample on GGX conductors (mrl_ggx_pdf_grad_* / mrl_ggx_sample_grad_*): kernels + calls
 //   merl_table_dir_grad.hip  the same on RGB tables (mrl_table_grad_dir_batch / _queue)
 //   merl_nch_dir_grad.hip  the same on n-channel tables (mrl_table_grad_dir_batch_nch / _queue_nch)
 //   merl_rgl_dir_grad.hip  the same on RGB RGL materials (mrl_rgl_grad_dir_batch / _queue)
@@ -250,6 +251,10 @@ struct DirGradFamily {
     // entry (null where the call goes without it; nullptr itself when the call lists none)
     std::function<hipError_t(const mrl::BatchArgs &a, const float *g, float *grad_wi, float *grad_wo, void *const *extra)> launch;
     size_t cap_bytes = 0;                        // host arrays: > 0, chunks so small that the staging slot stays below it
+    // the second input of a unit, DirGradCall::wo / BatchArgs::wo: a direction — or the two random numbers of the sample gradient
+    // (merl_ggx_sample_grad.hip: 8, "u"; that family has no grad_wo)
+    size_t second_bytes = 12;
+    const char *second_name = "wo";
 };
 // checks in the order the headers document, then f.launch on the caller's device arrays or chunk by chunk on staged host arrays
 int grad_dir_call(mrl_ctx *ctx, const DirGradCall &c, const DirGradFamily &f);

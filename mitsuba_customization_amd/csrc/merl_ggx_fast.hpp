@@ -319,6 +319,45 @@ MRL_HD GgxDirGrad ggx_eval_dir_grad(const GgxConsts &g, float wix, float wiy, fl
     return r;
 }
 
+// ---- the gradient of pdf (merl_ggx_sample_grad.hip) ----
+// P = D(m) G1(a) / (4 a_z) with a, b, h, m as above: ln P = ln D(m_z) + ln G1(a_z) - ln a_z, so with A = g P
+//     d/da = A (dlnD/dm_z (e_z - m m_z) / |h| + (dlnG1/da_z - 1/a_z) e_z)        d/db = A dlnD/dm_z (e_z - m m_z) / |h|
+//     d/dalpha = A (dlnD/dalpha + dlnG1(a)/dalpha)
+// the same twins, the same pull-back through the two normalisations and the same selects at the end as ggx_eval_dir_grad.
+struct GgxPdfGrad { float wi[3], wo[3], alpha; };
+MRL_HD GgxPdfGrad ggx_pdf_grad(const GgxConsts &g, float wix, float wiy, float wiz, float wox, float woy, float woz, float g32)
+{
+#pragma clang fp contract(off)
+    const Dir di = dir_f32(wix, wiy, wiz), dout = dir_f32(wox, woy, woz);
+    const Vec3 a = unit(di), b = unit(dout);
+    const double hx = a.x + b.x, hy = a.y + b.y, hz = a.z + b.z;
+    double L, rL;
+    sqrt_rsqrt(__builtin_fma(hx, hx, __builtin_fma(hy, hy, hz * hz)), L, rL);
+    const Vec3 m = { hx * rL, hy * rL, hz * rL };
+    double kD, kGa, inv_az, lD, lGa;
+    const double D = ggx_D_dz(g, m, kD);
+    const double G1a = ggx_G1_dz(g, a, m, kGa, inv_az);
+    (void)ggx_D_dlog(g, m, lD);
+    (void)ggx_G1_dlog(g, a, m, lGa);
+    const double A = (double)g32 * (D * G1a * (0.25 * inv_az));
+    const double p = A * kD * rL;
+    const double tx = p * -(m.x * m.z), ty = p * -(m.y * m.z), tz = p * __builtin_fma(m.x, m.x, m.y * m.y);
+    const double vaz = __builtin_fma(A, kGa - inv_az, tz);
+    const double da = __builtin_fma(a.x, tx, __builtin_fma(a.y, ty, a.z * vaz));
+    const double db = __builtin_fma(b.x, tx, __builtin_fma(b.y, ty, b.z * tz));
+    const float poison = cos_or_nan32((wix + wiy + wiz), wox, woy, woz, true);
+    const bool live = (wiz > 0.0f) && (woz > 0.0f) && (poison == poison) && D != 0.0 && G1a != 0.0;
+    GgxPdfGrad r;
+    r.wi[0] = live ? (float)(__builtin_fma(-a.x, da, tx) * di.rs) : 0.0f;
+    r.wi[1] = live ? (float)(__builtin_fma(-a.y, da, ty) * di.rs) : 0.0f;
+    r.wi[2] = live ? (float)(__builtin_fma(-a.z, da, vaz) * di.rs) : 0.0f;
+    r.wo[0] = live ? (float)(__builtin_fma(-b.x, db, tx) * dout.rs) : 0.0f;
+    r.wo[1] = live ? (float)(__builtin_fma(-b.y, db, ty) * dout.rs) : 0.0f;
+    r.wo[2] = live ? (float)(__builtin_fma(-b.z, db, tz) * dout.rs) : 0.0f;
+    r.alpha = live ? (float)(A * (lD + lGa)) : 0.0f;
+    return r;
+}
+
 // sin / cos of 2 pi u for u in [0,1): only the normal-incidence branch of the sampler needs it.  That branch is taken
 // when the stretched s_z >= 0.99999, i.e. alpha tan(theta_i) < 4.47e-3: almost never at alpha >= 0.1, but for every
 // incident direction up to 77 degrees at alpha = 1e-3 — for smooth materials it is the sampler's main branch.
@@ -407,6 +446,153 @@ __device__ __forceinline__ bool ggx_sample(const GgxConsts &g, const Vec3 &in, f
     weight[1] = ok ? (float)(fresnel_conductor(g, 1, c) * G1o) : 0.0f;
     weight[2] = ok ? (float)(fresnel_conductor(g, 2, c) * G1o) : 0.0f;
     return ok;
+}
+
+// ---- the gradient of sample (merl_ggx_sample_grad.hip) ----
+// (wo', p', w') = ggx_sample(wi, u) before its results are rounded to Float, differentiated in wi and in (alpha, eta, k) on the
+// branch the forward call takes — every select of ggx_sample above is held fixed, and so is u.  The forward chain is recomputed
+// with ggx_sample's own expressions for out.z, c and p and its (float)out.z > 0 test, then ONE reverse sweep carries the seven
+// cotangents go = (g_wo xyz, g_pdf, g_weight rgb) back:
+//     w'_c = F_c(c) G1(o)          c~ = G1(o) sum g_w F'_c          weight on ln G1(o):  W = G1(o) sum g_w F_c
+//     p'   = D(m) G1(i) / (4 i_z)  weight on ln p':  P = g_p p'
+//     o    = 2 c m - i             o~ = g_wo + W dlnG1/do_z e_z;    c~ += 2 o~ . m;   m~ = 2 c o~ + c~ i + P dlnD/dm_z e_z
+//                                  i~ = -o~ + c~ m + P (dlnG1/di_z - 1/i_z) e_z
+//     m    = n / |n|, n = (-m_x, -m_y, 1):  n~ = (m~ - m (m . m~)) / |n|   (which also projects D's sphere gradient)
+//     (m_x, m_y) = alpha R(phi) (sl_x, sl_y):  alpha~ += n~ . d n / d alpha, and through the rotation to sl~, cos~, sin~
+//     general branch: sl_y = Z sqrt(1 + sl_x^2) (Z is a function of u alone) and sl_x = sl_x(B), B = tan(theta) of the stretched
+//     direction = alpha |i_xy| / i_z, (cos phi, sin phi) = i_xy / |i_xy| (the stretch cancels): B~ and the rotation go to i~, alpha~.
+//     normal-incidence branch: the slopes depend on u alone and phi = 0.
+// d sl_x / d B is taken from the closed form of the forward's root: with T = 1 / (A^2 - 1) and R = sqrt(1 + B^2 - A^2) the forward's
+// disc is T^2 A^2 R^2, so sl_x = T (B + s A R), s = -+1 the sign the forward's selects fix — the forward's own expression for disc
+// cancels to 0 at A -> 0 and its derivative cannot be taken term by term.  A = u0 (1 + sqrt(1 + B^2)) - 1 gives A' = u0 B / sqrt(1 + B^2).
+// A unit is dead exactly when the forward rejects it (pdf = 0): selects at the end, its values are garbage and its go may be NaN.
+struct GgxSampleGrad { float wi[3], params[7]; };
+MRL_HD GgxSampleGrad ggx_sample_grad(const GgxConsts &g, const double eta[3], const double k[3], float wix, float wiy, float wiz,
+                                     float u0, float u1, const float go[7])
+{
+#pragma clang fp contract(off)
+    const Dir di = dir_f32(wix, wiy, wiz);
+    const Vec3 in = unit(di);
+    const double al = g.alpha;
+    // ---- forward, as ggx_sample
+    double sx = al * in.x, sy = al * in.y, sz = in.z;
+    double sl, srs;
+    sqrt_rsqrt(__builtin_fma(sx, sx, __builtin_fma(sy, sy, sz * sz)), sl, srs);
+    sx *= srs; sy *= srs; sz *= srs;
+    double slx, sly, cp = 1.0, sp = 0.0;
+    double u2 = (double)u1;
+    const bool general = sz < 0.99999;
+    double B = 0.0, slx_B = 0.0, sly_slx = 0.0, inv_rho = 0.0;       // B, d sl_x / d B, d sl_y / d sl_x, 1 / |i_xy|
+    if (general) {
+        double rho, rrho;
+        sqrt_rsqrt(__builtin_fma(sx, sx, sy * sy), rho, rrho);
+        cp = sx * rrho; sp = sy * rrho;
+        inv_rho = al * srs * rrho;
+        const double inv_tan = sz * rrho;
+        const double tan_i = rho * rcp_nr(sz);
+        const double q1 = sqrt_fast(__builtin_fma(tan_i, tan_i, 1.0));
+        const double G1 = 2.0 * rcp_nr(1.0 + q1);
+        double A = __builtin_fma(2.0 * (double)u0, rcp_nr(G1), -1.0);
+        if (__builtin_fabs(A) == 1.0) A -= (A > 0 ? 1.0 : -1.0) * 1e-12;
+        const double tmp = rcp_nr(__builtin_fma(A, A, -1.0));
+        B = tan_i;
+        const double disc = B * B * tmp * tmp - (A * A - B * B) * tmp;
+        const double Dq = disc > 0.0 ? sqrt_fast(disc) : 0.0;
+        const double s1 = B * tmp - Dq, s2 = B * tmp + Dq;
+        const bool first = A < 0.0 || s2 > inv_tan;
+        slx = first ? s1 : s2;
+        double S;
+        if (u2 > 0.5) { S = 1.0; u2 = 2.0 * (u2 - 0.5); }
+        else { S = -1.0; u2 = 2.0 * (0.5 - u2); }
+        const double num = u2 * (u2 * (u2 * (-0.365728915865723) + 0.790235037209296) - 0.424965825137544) + 0.000152998850436920;
+        const double den = u2 * (u2 * (u2 * (u2 * 0.169507819808272 - 0.397203533833404) - 0.232500544458471) + 1.0) - 0.539825872510702;
+        const double n2 = __builtin_fma(slx, slx, 1.0);
+        sly = S * num * rcp_nr(den) * sqrt_fast(n2);
+        // d sl_x / d B from sl_x = T (B + s A R)
+        const double sgn = (first ? -1.0 : 1.0) * (tmp < 0.0 ? -1.0 : 1.0) * (A < 0.0 ? -1.0 : 1.0);
+        const double s = (disc > 0.0 && A != 0.0) ? sgn : 0.0;
+        double R, rR;
+        sqrt_rsqrt((q1 - A) * (q1 + A), R, rR);
+        const double A_B = (double)u0 * B * rcp_nr(q1);
+        const double AR_B = __builtin_fma(A_B, R, A * __builtin_fma(-A, A_B, B) * rR);
+        slx_B = tmp * __builtin_fma(s, AR_B, __builtin_fma(-2.0 * A * A_B, slx, 1.0));
+        sly_slx = sly * slx * rcp_nr(n2);
+    } else {
+        const double q = (double)u0 * rcp_nr(1.0 - (double)u0);
+        const double r = q > 0.0 ? sqrt_fast(q) : 0.0;
+        double s2pi, c2pi;
+        sincos_2pi(u2, s2pi, c2pi);
+        slx = r * c2pi; sly = r * s2pi;
+    }
+    const double rx = cp * slx - sp * sly, ry = sp * slx + cp * sly;
+    const double mx = rx * al, my = ry * al;
+    double nl, nrm;
+    sqrt_rsqrt(__builtin_fma(mx, mx, __builtin_fma(my, my, 1.0)), nl, nrm);
+    const Vec3 m = { -mx * nrm, -my * nrm, nrm };
+    const double c = __builtin_fma(in.x, m.x, __builtin_fma(in.y, m.y, in.z * m.z));
+    const Vec3 out = { __builtin_fma(2.0 * c, m.x, -in.x), __builtin_fma(2.0 * c, m.y, -in.y), __builtin_fma(2.0 * c, m.z, -in.z) };
+    double kD, kGi, kGo, inv_iz, inv_oz, lD, lGi, lGo;
+    const double D = ggx_D_dz(g, m, kD);
+    const double G1i = ggx_G1_dz(g, in, m, kGi, inv_iz);
+    const double G1o = ggx_G1_dz(g, out, m, kGo, inv_oz);
+    (void)ggx_D_dlog(g, m, lD);
+    (void)ggx_G1_dlog(g, in, m, lGi);
+    (void)ggx_G1_dlog(g, out, m, lGo);
+    const double p = D * G1i * 0.25 * inv_iz;
+    // ggx_sample's decision restated, and the wi.z > 0 its callers add; a NaN / inf wi fails it as it fails theirs: its c is NaN.
+    // The same expressions, NOT the same instructions: ggx_sample leaves contraction to the compiler and takes D, G1 and the
+    // material's constants from ggx_D, ggx_G1 and the GgxConsts constructor, this copy has contraction off and takes them from the
+    // twins and ggx_consts_exact, so out.z, c and p can differ from the forward's in the last bits and a unit within that of a
+    // threshold can be decided the other way.  The tests hold the two dead sets equal on every unit they run.
+    const bool ok = (wiz > 0.0f) && (out.z > 0.0) && (c > 0.0) && (p > 0.0) && ((float)out.z > 0.0f);
+    // ---- reverse
+    const double gp = (double)go[3];
+    double sF = 0.0, sdF = 0.0, g_eta[3], g_k[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        double dF, fE, fQ;
+        const double F = fresnel_conductor_dc(g, ch, c, dF);
+        (void)fresnel_conductor_d(g, ch, c, fE, fQ);
+        const double gw = (double)go[4 + ch] * G1o;
+        sF = __builtin_fma(gw, F, sF);
+        sdF = __builtin_fma(gw, dF, sdF);
+        const double e2 = eta[ch] * eta[ch], k2 = k[ch] * k[ch];
+        g_eta[ch] = gw * (2.0 * eta[ch] * __builtin_fma(4.0 * k2, fQ, fE));
+        // F is even in k: at k = 0 the derivative is 0 whatever fE and fQ are
+        g_k[ch] = k[ch] == 0.0 ? 0.0 : gw * (2.0 * k[ch] * __builtin_fma(4.0 * e2, fQ, -fE));
+    }
+    const double P = gp * p;
+    double g_alpha = __builtin_fma(P, lD + lGi, sF * lGo);
+    const double obx = (double)go[0], oby = (double)go[1], obz = __builtin_fma(sF, kGo, (double)go[2]);
+    const double cb = __builtin_fma(2.0, __builtin_fma(obx, m.x, __builtin_fma(oby, m.y, obz * m.z)), sdF);
+    const double mbx = __builtin_fma(2.0 * c, obx, cb * in.x), mby = __builtin_fma(2.0 * c, oby, cb * in.y);
+    const double mbz = __builtin_fma(2.0 * c, obz, __builtin_fma(cb, in.z, P * kD));
+    double ibx = __builtin_fma(cb, m.x, -obx), iby = __builtin_fma(cb, m.y, -oby);
+    double ibz = __builtin_fma(cb, m.z, __builtin_fma(P, kGi - inv_iz, -obz));
+    const double md = __builtin_fma(m.x, mbx, __builtin_fma(m.y, mby, m.z * mbz));
+    const double mxb = -(__builtin_fma(-m.x, md, mbx) * nrm), myb = -(__builtin_fma(-m.y, md, mby) * nrm);     // cotangents of m_x, m_y
+    g_alpha = __builtin_fma(mxb, rx, __builtin_fma(myb, ry, g_alpha));
+    const double rxb = al * mxb, ryb = al * myb;
+    if (general) {
+        const double slyb = __builtin_fma(-sp, rxb, cp * ryb);
+        const double slxb = __builtin_fma(cp, rxb, __builtin_fma(sp, ryb, slyb * sly_slx));
+        const double cpb = __builtin_fma(slx, rxb, sly * ryb), spb = __builtin_fma(-sly, rxb, slx * ryb);
+        const double Bb = slxb * slx_B * B;                          // B~ B: every use of B~ carries the factor B
+        const double t = __builtin_fma(-sp, cpb, cp * spb) * inv_rho;
+        g_alpha = __builtin_fma(Bb, al * g.inv_alpha2, g_alpha);
+        ibx += __builtin_fma(Bb * inv_rho, cp, -(sp * t));
+        iby += __builtin_fma(Bb * inv_rho, sp, cp * t);
+        ibz -= Bb * inv_iz;
+    }
+    const double dd = __builtin_fma(in.x, ibx, __builtin_fma(in.y, iby, in.z * ibz));
+    GgxSampleGrad r;
+    r.wi[0] = ok ? (float)(__builtin_fma(-in.x, dd, ibx) * di.rs) : 0.0f;
+    r.wi[1] = ok ? (float)(__builtin_fma(-in.y, dd, iby) * di.rs) : 0.0f;
+    r.wi[2] = ok ? (float)(__builtin_fma(-in.z, dd, ibz) * di.rs) : 0.0f;
+    r.params[0] = ok ? (float)g_alpha : 0.0f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) { r.params[1 + ch] = ok ? (float)g_eta[ch] : 0.0f; r.params[4 + ch] = ok ? (float)g_k[ch] : 0.0f; }
+    return r;
 }
 
 } // namespace fast

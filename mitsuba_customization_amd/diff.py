@@ -241,6 +241,120 @@ def _apply(gpu, wi, wo, forward_call, backward_call, mat, material, tables=None,
     return _Eval.apply(wi, wo, forward_call, backward_call, m.gradients, *m.values)
 
 
+def _per_material_sums(gpu, per_unit, mat, ids, values):
+    """The per-unit parameter gradients of a pdf / sample gradient call — [n, 7] f32, or [n] for grad_alpha — summed in f64 on the device
+    into one [7] (or scalar) per tensor of `values` (the materials `ids`): the whole array for a call on one material, index_add_ by id
+    for a call with ids (a unit whose id names nothing in range adds nothing: its row is zero anyway)."""
+    rows = per_unit.double()
+    if mat is None:
+        total = rows.sum(0)
+        return [total.to(t.device) for t in values]
+    count = gpu.material_count()
+    ok = (mat >= 0) & (mat < count)
+    sums = torch.zeros((count,) + tuple(rows.shape[1:]), dtype=torch.float64, device=rows.device)
+    sums.index_add_(0, torch.where(ok, mat, torch.zeros_like(mat)).long(), torch.where(ok.reshape((-1,) + (1,) * (rows.dim() - 1)), rows, torch.zeros_like(rows)))
+    return [sums[mid].to(t.device) for mid, t in zip(ids, values)]
+
+
+class _GgxPdf(torch.autograd.Function):
+    """forward MerlHip.pdf, backward one MerlHip.ggx_pdf_grad call for the outputs the graph needs (include/merl_hip_diff_sample.h)"""
+    @staticmethod
+    def forward(ctx, wi, wo, gpu, mat, material, ids, *values):
+        wi, wo = wi.contiguous(), wo.contiguous()
+        ctx.save_for_backward(wi, wo)
+        ctx.call = (gpu, mat, material, ids)
+        ctx.values = values
+        return gpu.pdf(wi, wo, mat=mat, material=material)
+
+    @staticmethod
+    def backward(ctx, grad_pdf):
+        wi, wo = ctx.saved_tensors
+        gpu, mat, material, ids = ctx.call
+        in_values = [None] * len(ctx.values)
+        needed = [i for i, need in enumerate(ctx.needs_input_grad[6:]) if need]
+        # only what the graph asks for: the other output pointers are NULL and those gradients are neither computed nor written
+        want = tuple(name for name, need in zip(("wi", "wo", "alpha"), (*ctx.needs_input_grad[:2], bool(needed))) if need)
+        grads = {}
+        if want:
+            out = gpu.ggx_pdf_grad(wi, wo, grad_pdf.contiguous(), mat=mat, material=material, want=want)
+            grads = dict(zip(want, (out,) if len(want) == 1 else out))
+        if needed:                                              # the pdf depends on alpha alone: entry 0 of a tensor's gradient
+            sums = _per_material_sums(gpu, grads["alpha"], mat, ids, ctx.values)
+            for i in needed:
+                in_values[i] = torch.zeros(7, dtype=torch.float64, device=sums[i].device)
+                in_values[i][0] = sums[i]
+        return (grads.get("wi"), grads.get("wo"), None, None, None, None, *in_values)
+
+
+class _GgxSample(torch.autograd.Function):
+    """forward MerlHip.sample -> (wo, pdf, weight), backward one MerlHip.ggx_sample_grad call on the packed cotangent [n, 7] for the
+    outputs the graph needs; u is held fixed"""
+    @staticmethod
+    def forward(ctx, wi, u, gpu, mat, material, ids, *values):
+        wi, u = wi.contiguous(), u.contiguous()
+        ctx.save_for_backward(wi, u)
+        ctx.call = (gpu, mat, material, ids)
+        ctx.values = values
+        return tuple(gpu.sample(wi, u, mat=mat, material=material))
+
+    @staticmethod
+    def backward(ctx, g_wo, g_pdf, g_weight):
+        wi, u = ctx.saved_tensors
+        gpu, mat, material, ids = ctx.call
+        n = wi.shape[0]
+        in_values = [None] * len(ctx.values)
+        needed = [i for i, need in enumerate(ctx.needs_input_grad[6:]) if need]
+        want = tuple(name for name, need in zip(("wi", "params"), (ctx.needs_input_grad[0], bool(needed))) if need)
+        grads = {}
+        if want:
+            g = torch.zeros((n, 7), dtype=torch.float32, device=wi.device)         # a None incoming gradient stays zero
+            if g_wo is not None:
+                g[:, 0:3] = g_wo
+            if g_pdf is not None:
+                g[:, 3] = g_pdf
+            if g_weight is not None:
+                g[:, 4:7] = g_weight
+            out = gpu.ggx_sample_grad(wi, u, g, mat=mat, material=material, want=want)
+            grads = dict(zip(want, (out,) if len(want) == 1 else out))
+        if needed:
+            sums = _per_material_sums(gpu, grads["params"], mat, ids, ctx.values)
+            for i in needed:
+                in_values[i] = sums[i]
+        return (grads.get("wi"), None, None, None, None, None, *in_values)
+
+
+def _ggx_values(ctx, mat, material, params):
+    """(ids, tensors) of params= after the materials have received the tensors' current values (_Materials.refresh)"""
+    if params is None:
+        return (), ()
+    m = _Materials(ctx, mat, material, None, params)
+    m.refresh()
+    return tuple(mid for _, mid, _ in m.entries), m.values
+
+
+def ggx_pdf(ctx, wi, wo, mat=None, material: int = 0, params=None):
+    """MerlHip.pdf(wi, wo, mat, material) of the context `ctx` — the same bits —, differentiable in wi and wo: what an MIS weight needs.
+    The materials must be GGX conductors: the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat=
+    a unit whose id names no live GGX material receives a zero gradient.  Backward is one MerlHip.ggx_pdf_grad call
+    (include/merl_hip_diff_sample.h) for the outputs the graph needs.
+    params=: as in ggx_eval(): an f64 [7] tensor (alpha, eta rgb, k rgb) or {id: tensor}; forward does update_ggx on change.  Their
+    gradient is the per-unit grad_alpha summed in f64 on the device (.double().sum(0), with ids index_add_ by id); the pdf depends on
+    alpha alone, so only entry 0 is non-zero."""
+    ids, values = _ggx_values(ctx, mat, material, params)
+    return _GgxPdf.apply(wi, wo, ctx, mat, material, ids, *values)
+
+
+def ggx_sample(ctx, wi, u, mat=None, material: int = 0, params=None):
+    """MerlHip.sample(wi, u, mat, material) of the context `ctx` — (wo, pdf, weight), the same bits —, differentiable in wi: the sampled
+    direction, its pdf and its weight move with the shading frame, so the next bounce's gradient flows through this one's sampler.  u
+    is held fixed and the function is differentiated on the branch the forward call takes (include/merl_hip_diff_sample.h, DESIGN.md
+    §5t); a rejected sample receives a zero gradient.  Backward is one MerlHip.ggx_sample_grad call on the packed cotangent for the
+    outputs the graph needs.
+    params=: as in ggx_pdf(); their gradient is the per-unit grad_params summed in f64 on the device."""
+    ids, values = _ggx_values(ctx, mat, material, params)
+    return _GgxSample.apply(wi, u, ctx, mat, material, ids, *values)
+
+
 def ggx_eval(ctx, wi, wo, mat=None, material: int = 0, params=None):
     """MerlHip.eval(wi, wo, mat, material) of the context `ctx`, differentiable in wi and wo.  The materials must be GGX conductors:
     the backward pass of a single material of another kind raises MRL_ERR_MATERIAL, and with mat= a unit whose id names no live GGX

@@ -70,6 +70,8 @@ ABI_SYMBOLS = (
 FIT_ABI_SYMBOLS = ("mrl_ggx_grad_batch",)
 # every symbol include/merl_hip_diff.h declares, the differentiation extension of the ABI (exported by the same library)
 DIFF_ABI_SYMBOLS = ("mrl_ggx_grad_dir_batch", "mrl_ggx_grad_dir_queue")
+# every symbol include/merl_hip_diff_sample.h declares: the gradients of pdf and of sample on GGX conductors
+DIFF_SAMPLE_ABI_SYMBOLS = ("mrl_ggx_pdf_grad_batch", "mrl_ggx_pdf_grad_queue", "mrl_ggx_sample_grad_batch", "mrl_ggx_sample_grad_queue")
 # every symbol include/merl_hip_diff_table.h declares: the direction gradient of eval on RGB table materials
 DIFF_TABLE_ABI_SYMBOLS = ("mrl_table_grad_dir_batch", "mrl_table_grad_dir_queue")
 # every symbol include/merl_hip_diff_nch.h declares: the same gradient on n-channel table materials
@@ -276,6 +278,14 @@ _CALLS["batch", "rgl_spectral_values_grad"] = ("mrl_rgl_spectral_values_grad_bat
 _CALLS["queue", "rgl_spectral_values_grad"] = ("mrl_rgl_spectral_values_grad_queue",
                                                ("wavelengths", "n_wavelengths", "grad_values") + _FAMILIES["queue"][1] + _RGL_SPECTRAL_TARGETS, (_WI, _WO), ())
 _CALLS["material", "update_rgl_spectral_values"] = ("mrl_material_update_rgl_spectral_values", ("id", "spectra", "flags"), (), ())
+
+# the gradients of pdf and of sample on GGX conductors (include/merl_hip_diff_sample.h): three input streams, the family's middle
+# parameters, and per-unit outputs any of which may be None — ("name", columns) with None for [n]
+_PDF_GRAD_IO = ((_WI, _WO, ("grad_pdf", None)), (("grad_wi", 3), ("grad_wo", 3), ("grad_alpha", None)))
+_SAMPLE_GRAD_IO = ((_WI, _U, ("grad_out", 7)), (("grad_wi", 3), ("grad_params", 7)))
+for _family in ("batch", "queue"):
+    _CALLS[_family, "ggx_pdf_grad"] = ("mrl_ggx_pdf_grad_" + _family, _FAMILIES[_family][1]) + _PDF_GRAD_IO
+    _CALLS[_family, "ggx_sample_grad"] = ("mrl_ggx_sample_grad_" + _family, _FAMILIES[_family][1]) + _SAMPLE_GRAD_IO
 
 
 _lib = None
@@ -1326,6 +1336,51 @@ class MerlHip:
         in -> device tensors out.  Returns the gradient wanted, or a tuple in want's order."""
         return self._grad_dir_spectral_call("mrl_rgl_grad_dir_spectral_batch", wi, wo, wavelengths, grad_values, mat, material, n_wavelengths, want, out)
 
+    def _unit_grad_call(self, family, mode, ins, mat, material, want, out, queue=None):
+        """One call of include/merl_hip_diff_sample.h through its row of _CALLS: per-unit outputs, any of which may be left out.  ins: the
+        three input arrays; want: a non-empty subset of the row's output names (without "grad_"), in their order; out: one array, or
+        a tuple in want's order; queue: the (queue, count, capacity) of the queue form, whose outputs allocated here start from zeros.
+        Returns the gradient wanted, or a tuple in want's order."""
+        symbol, _, in_streams, out_streams = _CALLS[family, mode]
+        names = tuple(name[len("grad_"):] for name, _ in out_streams)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in names for w in want) or list(want) != [w for w in names if w in want]:
+            raise ValueError(f"want: a non-empty subset of {names}, in that order")
+        wi = ins[0]
+        n = int(wi.shape[0])
+        if queue is None:
+            self._prep(wi)
+        middle = (n,) if queue is None else self._queue(wi, *queue)
+        alloc = self._empty if queue is None else self._zeros
+        shapes = {name: ((n,) if cols is None else (n, cols)) for name, (_, cols) in zip(names, out_streams)}
+        if out is None:
+            outs = tuple(alloc(wi, shapes[w]) for w in want)
+        else:
+            outs = (out,) if len(want) == 1 and not isinstance(out, (tuple, list)) else tuple(out)
+            if len(outs) != len(want):
+                raise ValueError(f"out: {len(want)} arrays wanted, got {len(outs)}")
+        by_name = dict(zip(want, outs))
+        self._check(getattr(self._lib, symbol)(self._ctx, *(_addr(x, np.float32, cols, n, name) for x, (name, cols) in zip(ins, in_streams)),
+                                               _addr(mat, np.int32, None, n, "mat"), material, *middle,
+                                               *(_addr(by_name.get(name), np.float32, cols, n, "grad_" + name)
+                                                 for name, (_, cols) in zip(names, out_streams))), symbol)
+        return outs[0] if len(outs) == 1 else outs
+
+    def ggx_pdf_grad(self, wi, wo, grad_pdf, mat=None, material: int = 0, want=("wi", "wo", "alpha"), out=None):
+        """The gradient of pdf on GGX materials (mrl_ggx_pdf_grad_batch, include/merl_hip_diff_sample.h): per unit grad_wi = grad_pdf
+        dP / d wi and the same in wo, [n, 3] f32, and grad_alpha = grad_pdf dP / d alpha, [n] f32 — per unit, the caller sums it; all
+        overwritten.  grad_pdf: [n] f32.  A dead unit, and with mat= a unit whose id names no live GGX material, gets zeros.  want:
+        which of the three to compute.  Same conventions as ggx_grad_dir()."""
+        return self._unit_grad_call("batch", "ggx_pdf_grad", (wi, wo, grad_pdf), mat, material, want, out)
+
+    def ggx_sample_grad(self, wi, u, grad_out, mat=None, material: int = 0, want=("wi", "params"), out=None):
+        """The gradient of sample on GGX materials (mrl_ggx_sample_grad_batch, include/merl_hip_diff_sample.h).  grad_out: [n, 7] f32 =
+        (g_wo xyz, g_pdf, g_weight rgb).  Per unit grad_wi [n, 3] = sum_j grad_out_j d y_j / d wi and grad_params [n, 7] = the same in
+        (alpha, eta rgb, k rgb) — per unit, the caller sums it —, y = (wo', pdf', weight') on the branch the forward call takes, u
+        held fixed; both overwritten.  A unit the forward call rejects, and with mat= a unit whose id names no live GGX material, gets
+        zeros.  want: which of the two to compute.  Same conventions as ggx_grad_dir()."""
+        return self._unit_grad_call("batch", "ggx_sample_grad", (wi, u, grad_out), mat, material, want, out)
+
     def pdf(self, wi, wo, mat=None, material: int = 0, out=None):
         return _stream_call(self, "batch", "pdf", (wi, wo), out, mat=mat, material=material)
 
@@ -1397,6 +1452,16 @@ class MerlHip:
         """ggx_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_grad_dir_queue); other slots of `out` stay as they
         are (outputs allocated here start from zeros)."""
         return self._grad_dir_call("mrl_ggx_grad_dir_queue", wi, wo, grad_rgb, mat, material, want, out, queue=(queue, count, capacity))
+
+    def ggx_pdf_grad_queue(self, wi, wo, grad_pdf, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo", "alpha"), out=None):
+        """ggx_pdf_grad() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_pdf_grad_queue); other slots of `out` stay as they are
+        (outputs allocated here start from zeros)."""
+        return self._unit_grad_call("queue", "ggx_pdf_grad", (wi, wo, grad_pdf), mat, material, want, out, queue=(queue, count, capacity))
+
+    def ggx_sample_grad_queue(self, wi, u, grad_out, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "params"), out=None):
+        """ggx_sample_grad() of the slots queue[0 .. min(count, capacity)) (mrl_ggx_sample_grad_queue); other slots of `out` stay as
+        they are (outputs allocated here start from zeros)."""
+        return self._unit_grad_call("queue", "ggx_sample_grad", (wi, u, grad_out), mat, material, want, out, queue=(queue, count, capacity))
 
     def table_grad_dir_queue(self, wi, wo, grad_rgb, queue, count, mat=None, material: int = 0, capacity=None, want=("wi", "wo"), out=None):
         """table_grad_dir() of the slots queue[0 .. min(count, capacity)) (mrl_table_grad_dir_queue); other slots of `out` stay as
